@@ -6,7 +6,12 @@ Default (`--mode render`, the headline = BASELINE.json configs[1]): one "step" =
 tools/config_parser.py:17-24) with chunk = netchunk = 196608 (configs/exp_mofanerf.txt:9-10).  Weights are the seeded
 synthetic recipe (no checkpoint is downloadable), inputs are resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode render|fit|train]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode render|fit|train] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`, ...).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32; inputs are seeded, so two builds
+compare output for output).  `--full` adds everything else after the timed steps: the profiled roofline figures, the frame
+digest, the parity check against the CPU oracle, the labelled variants and the CPU baseline.
 
 `--gpus N` with N > 1 and no torchrun environment: bench.py re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>` (one process per
@@ -20,8 +25,8 @@ GPU, RCCL), so `python bench.py --gpus 8` alone produces the line; launched unde
   train   BASELINE configs[4]: run_train.py's step, N_rand = 4096 rays per GPU, texture encoder, forward + backward incl.
           weight gradients, ONE RCCL all-reduce of the flat gradient bucket, Adam; scaling "weak".
 
-Rank 0 prints ONE JSON line.  `roofline` is the dominant kernel of the mode (the MFMA kernel kind with the largest summed time):
-algorithmic FLOPs of its launches / their summed duration measured with HIP events on the launch stream, against the fp32 MFMA
+Rank 0 prints ONE JSON line.  Under `--full`, `roofline` is the dominant kernel of the mode (the MFMA kernel kind with the
+largest summed time): algorithmic FLOPs of its launches / their summed duration measured with HIP events on the launch stream, against the fp32 MFMA
 peak of 157.3 TFLOP/s.  `roofline_hbm` is SURVEY section 8d's second roofline: the HBM-bound compositing / resampling kernels of the
 same timed region, algorithmic bytes / HIP-event time against the 8 TB/s HBM peak.
 `cpu_baseline` times the CPU oracle on a bounded sample of the same workload (rank 0, N = 1 only).
@@ -284,11 +289,12 @@ def all_rays(L, K, dev, angle, b, n):
     return o, d
 
 
-def make_grad_step(mode, n, render, kw, dev, rank, L, K, bm, tex, exp, timed_comm=lambda fn: fn()):
+def make_grad_step(mode, n, render, kw, dev, rank, L, K, bm, tex, exp, timed_comm=lambda fn: fn(), outputs=None):
     """One step of BASELINE configs[2] (`fit`: run_fit.py:268-313, N_rand rays, forward + backward to codes / light, Adam) or configs[4]
     (`train`: run_train.py:278-364, N_rand rays per GPU, texture encoder, forward + backward incl. weight gradients, the flat gradient
     bucket's all-reduce, Adam) on `n` seeded rays of the H x W view — the step function the fit / train modes AND the headline
-    line's `variants.fit1024` / `variants.train4096` time."""
+    line's `variants.fit1024` / `variants.train4096` time.  `outputs` (a dict), if given, receives what the step returned to its
+    caller (fit: loss and rgb; train: loss), for `--dump-outputs`."""
     n_total = H * W
     o, d = all_rays(L, K, dev, 15.0 + rank, 0, n_total)
     idx = torch.from_numpy(np.random.default_rng(rank).choice(n_total, n, replace=False)).to(dev)
@@ -298,7 +304,13 @@ def make_grad_step(mode, n, render, kw, dev, rank, L, K, bm, tex, exp, timed_com
         cs = [t.clone().requires_grad_(True) for t in (bm, tex, exp)]
         light = torch.ones(1, device=dev, requires_grad=True)
         opts = [torch.optim.Adam(cs, lr=1e-3), torch.optim.Adam([light], lr=1e-3)]
-        return lambda i: msteps.fit_step(render, dict(kw), opts, H, W, K, rays_b, target, cs[0], cs[1], cs[2], light, chunk=n)[0]
+
+        def fit(i):
+            loss, rgb = msteps.fit_step(render, dict(kw), opts, H, W, K, rays_b, target, cs[0], cs[1], cs[2], light, chunk=n)
+            if outputs is not None:
+                outputs.update(loss=loss, rgb=rgb)
+            return loss
+        return fit
     kwt = dict(kw); kwt["perturb"] = 1.0
     render.train()
     params = list(kw["network_fn"].parameters()) + list(kw["network_fine"].parameters()) + list(render.grad_parameter())
@@ -308,7 +320,34 @@ def make_grad_step(mode, n, render, kw, dev, rank, L, K, bm, tex, exp, timed_com
     bucket.sync = lambda: timed_comm(sync0)
     uv = torch.rand(512, 512, 3, device=dev)
     bm_n = bm.expand(n, -1)
-    return lambda i: msteps.train_step(render, kwt, opt, bucket, H, W, K, rays_b, target, bm_n, uv, 3, chunk=n)
+
+    def train(i):
+        loss = msteps.train_step(render, kwt, opt, bucket, H, W, K, rays_b, target, bm_n, uv, 3, chunk=n)
+        if outputs is not None:
+            outputs.update(loss=loss)
+        return loss
+    return train
+
+
+MAX_DUMP_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy in float32.  Past MAX_DUMP_BYTES in all, the same fixed, seeded sample of
+    rows (first axis) is kept of every array, and the row numbers go to DIR/sample_rows.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > MAX_DUMP_BYTES:
+        rows = {v.shape[0] for v in arrays.values() if v.ndim > 0}
+        assert len(rows) == 1, f"arrays of {total} bytes with different row counts {sorted(rows)}: no common sample"
+        n = rows.pop()
+        per_row = sum(v.nbytes // n for v in arrays.values() if v.ndim > 0) + 8
+        keep = np.sort(np.random.default_rng(seed).choice(n, (MAX_DUMP_BYTES - 128 * (len(arrays) + 1)) // per_row, replace=False))
+        arrays = {k: (v[keep] if v.ndim > 0 else v) for k, v in arrays.items()}
+        arrays["sample_rows"] = keep.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
 
 
 def roofline_of(ms, launches, pflops, dt):
@@ -506,6 +545,13 @@ def main():
     ap.add_argument("--bulk-identities", type=int, default=2, help="identities of BASELINE configs[3]'s job shape (x 2 expressions x 3 views at 256^2 "
                     "through render_path with the texture encoder and the PNG sink) timed after the headline loop into variants.bulk256 (same conditions; 0 = skip)")
     ap.add_argument("--rays", type=int, default=None, help="fit / train: N_rand per GPU (default 1024 / 4096)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (render: rgb, disp, acc of the frame; "
+                         "fit: loss, rgb; train: loss), float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline, after the timed steps: roofline / roofline_hbm (per-kernel "
+                         "HIP events over the timed steps), whole_path_tflops, frame_sha256, parity, variants, cpu_baseline.  The options "
+                         "--cpu-*, --parity-rays, --variant-steps, --fit-steps, --train-steps and --bulk-identities act only under --full")
     a = ap.parse_args()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_spawn(a.gpus))
@@ -536,6 +582,7 @@ def main():
     n_total = H * W
     comm_ms = []                                                       # per-step collective time on this rank (N > 1)
     compute_ev = []                                                    # per-step time of this rank's row block (render, N > 1)
+    step_out = {}                                                      # fit / train: what the last step returned (--dump-outputs)
 
     def timed_comm(fn):
         if not mdist.active():
@@ -572,7 +619,7 @@ def main():
     else:
         n = a.rays or (1024 if a.mode == "fit" else 4096)
         units_per_step, scaling = n * world, "weak"
-        step = make_grad_step(a.mode, n, render, kw, dev, rank, L, K, bm, tex, exp, timed_comm)
+        step = make_grad_step(a.mode, n, render, kw, dev, rank, L, K, bm, tex, exp, timed_comm, step_out if a.dump_outputs else None)
 
     def sync():
         if mdist.active():
@@ -586,7 +633,8 @@ def main():
     compute_ev.clear()
     mem0 = torch.cuda.memory_allocated(dev)
     torch.cuda.reset_peak_memory_stats(dev)
-    lib.check(L.mofa_prof_begin(), "mofa_prof_begin")
+    if a.full:                                                         # per-kernel HIP events for the roofline figures
+        lib.check(L.mofa_prof_begin(), "mofa_prof_begin")
     t0 = time.perf_counter()
     for i in range(a.steps):
         last = step(a.warmup + i)
@@ -594,7 +642,8 @@ def main():
     dt = time.perf_counter() - t0
     NK = lib.PROF_KINDS
     ms, launches, pflops = (ctypes.c_double * NK)(), (ctypes.c_int64 * NK)(), (ctypes.c_double * NK)()
-    lib.check(L.mofa_prof_end(ms, launches, pflops), "mofa_prof_end")
+    if a.full:
+        lib.check(L.mofa_prof_end(ms, launches, pflops), "mofa_prof_end")
     peak_extra = torch.cuda.max_memory_allocated(dev) - mem0           # what one step allocates on top of the resident state
     dt = mdist.barrier_max(dt, dev)
     comm = sum(e0.elapsed_time(e1) for e0, e1 in comm_ms) / max(1, len(comm_ms)) if comm_ms else 0.0
@@ -609,38 +658,41 @@ def main():
         assert last.shape == (n_total, 5) and bool(torch.isfinite(last[:, :3]).all())
     else:
         assert bool(torch.isfinite(last).all())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"rgb": last[:, :3], "disp": last[:, 3], "acc": last[:, 4]} if a.mode == "render" else step_out)
 
     if rank == 0:
         units_per_s = units_per_step * a.steps / dt
-        # dominant kernel = the MFMA kernel kind with the largest summed time.  Its algorithmic FLOPs are 2*M*K*N of its
-        # launches; at the benchmark sizes nothing is padded (K, N multiples of 64, M a multiple of 256), except layer 0's
-        # K = 63 -> 64 inside the persistent kernel (0.1 %).
-        dom, roof = roofline_of(ms, launches, pflops, dt)
-        ksym, krole, kdesc = KERNELS[dom]
-        kname = f"{ksym} ({kdesc})"
-        traffic, tinfo = None, {}
-        # PMC-derived bytes/launch (separate --pmc passes), one record per kernel
-        tpath = os.path.join(ROOT, "profiles", "hbm_traffic_chain.json" if dom == 5 else "hbm_traffic.json")
-        if os.path.exists(tpath) and dom in (0, 5) and a.mode == "render" and ARCH == (8, 256, 10, 1024):
-            from mofanerf_amd import build as mbuild
-            tj = json.load(open(tpath))
-            digest = mbuild.csrc_digest()
-            # the counters were collected on a single-layer driver of the SAME kernel in separate --pmc passes (rocprofv3 cannot
-            # wrap this whole process); they are quoted only while they describe the kernel that just ran: same instantiation, and
-            # the kernel sources hash to what the passes were taken on — otherwise `traffic` is null and says why
-            if tj.get("csrc_sha256") == digest and tj.get("kernel", "").split(" ")[0] == kname.split(" ")[0]:
-                traffic = tj.get("bytes_per_launch")
-                tinfo = {"traffic_shape": tj.get("shape"), "traffic_algorithmic_bytes_same_shape": tj.get("algorithmic_bytes_per_launch"),
-                         "mfma_busy_fraction_pmc": tj.get("mfma_busy_fraction"), "traffic_csrc_sha256": digest[:16],
-                         "traffic_source": f"profiles/{os.path.basename(tpath)} (rocprofv3 --pmc passes on a driver that launches this kernel alone, "
-                                           "same kernel sources by hash; not this run)"}
-            else:
-                tinfo = {"traffic_source": f"null: profiles/{os.path.basename(tpath)} was taken on kernel sources {str(tj.get('csrc_sha256'))[:16]} / "
-                                           f"{tj.get('kernel')}, this build is {digest[:16]} / {kname.split(' ')[0]} — re-run tools/gpu_profile_round.sh"}
-        # SURVEY section 8d's second roofline: the HBM-bound ray kernels of the same timed region (compositing, resampling)
-        from mofanerf_amd import build as mbuild2
-        rpath = os.path.join(ROOT, "profiles", "hbm_traffic_rays.json")
-        roof_hbm = roofline_hbm_of(ms, launches, pflops, dt, json.load(open(rpath)) if os.path.exists(rpath) else None, mbuild2.csrc_digest())
+        if a.full:
+            # dominant kernel = the MFMA kernel kind with the largest summed time.  Its algorithmic FLOPs are 2*M*K*N of its
+            # launches; at the benchmark sizes nothing is padded (K, N multiples of 64, M a multiple of 256), except layer 0's
+            # K = 63 -> 64 inside the persistent kernel (0.1 %).
+            dom, roof = roofline_of(ms, launches, pflops, dt)
+            ksym, krole, kdesc = KERNELS[dom]
+            kname = f"{ksym} ({kdesc})"
+            traffic, tinfo = None, {}
+            # PMC-derived bytes/launch (separate --pmc passes), one record per kernel
+            tpath = os.path.join(ROOT, "profiles", "hbm_traffic_chain.json" if dom == 5 else "hbm_traffic.json")
+            if os.path.exists(tpath) and dom in (0, 5) and a.mode == "render" and ARCH == (8, 256, 10, 1024):
+                from mofanerf_amd import build as mbuild
+                tj = json.load(open(tpath))
+                digest = mbuild.csrc_digest()
+                # the counters were collected on a single-layer driver of the SAME kernel in separate --pmc passes (rocprofv3 cannot
+                # wrap this whole process); they are quoted only while they describe the kernel that just ran: same instantiation, and
+                # the kernel sources hash to what the passes were taken on — otherwise `traffic` is null and says why
+                if tj.get("csrc_sha256") == digest and tj.get("kernel", "").split(" ")[0] == kname.split(" ")[0]:
+                    traffic = tj.get("bytes_per_launch")
+                    tinfo = {"traffic_shape": tj.get("shape"), "traffic_algorithmic_bytes_same_shape": tj.get("algorithmic_bytes_per_launch"),
+                             "mfma_busy_fraction_pmc": tj.get("mfma_busy_fraction"), "traffic_csrc_sha256": digest[:16],
+                             "traffic_source": f"profiles/{os.path.basename(tpath)} (rocprofv3 --pmc passes on a driver that launches this kernel alone, "
+                                               "same kernel sources by hash; not this run)"}
+                else:
+                    tinfo = {"traffic_source": f"null: profiles/{os.path.basename(tpath)} was taken on kernel sources {str(tj.get('csrc_sha256'))[:16]} / "
+                                               f"{tj.get('kernel')}, this build is {digest[:16]} / {kname.split(' ')[0]} — re-run tools/gpu_profile_round.sh"}
+            # SURVEY section 8d's second roofline: the HBM-bound ray kernels of the same timed region (compositing, resampling)
+            from mofanerf_amd import build as mbuild2
+            rpath = os.path.join(ROOT, "profiles", "hbm_traffic_rays.json")
+            roof_hbm = roofline_hbm_of(ms, launches, pflops, dt, json.load(open(rpath)) if os.path.exists(rpath) else None, mbuild2.csrc_digest())
         fwd = flops_per_ray(True)
         work = {"render": fwd, "fit": 2 * fwd, "train": 3 * fwd}[a.mode]    # + backward-data (+ weight gradients)
         metric = {"render": "rendered rays/sec (64c+128f samples) at 512^2 novel-view",
@@ -666,11 +718,12 @@ def main():
                        "parallelism": par,
                        "gflop_per_ray_folded": round(work / 1e9, 4),
                        "gflop_per_ray_nominal": round(work / fwd * flops_per_ray(False) / 1e9, 4)},
-            "whole_path_tflops": round(work * units_per_s / 1e12, 2),
-            "roofline": {**{k: v for k, v in roof.items() if k != "other_mfma_kernels"}, "traffic": traffic,
-                         "other_mfma_kernels": roof["other_mfma_kernels"], **tinfo},
-            "roofline_hbm": roof_hbm,
         }
+        if a.full:
+            out["whole_path_tflops"] = round(work * units_per_s / 1e12, 2)
+            out["roofline"] = {**{k: v for k, v in roof.items() if k != "other_mfma_kernels"}, "traffic": traffic,
+                               "other_mfma_kernels": roof["other_mfma_kernels"], **tinfo}
+            out["roofline_hbm"] = roof_hbm
         if mdist.active():
             out["rccl_ranks"] = world
             out["backend"] = torch.distributed.get_backend()
@@ -682,18 +735,18 @@ def main():
                                  "avg_ms_per_step_rank0": round(comm, 4)}
             if compute_minmax is not None:
                 out["collective"]["compute_ms_per_step_min_over_ranks"], out["collective"]["compute_ms_per_step_max_over_ranks"] = compute_minmax
-        if a.mode == "render":
+        if a.full and a.mode == "render":
             # what the timed region produced, so that an N > 1 line can be checked against the N = 1 line of the same view: the rows are
             # rendered by different ranks but chunk invariance is bit-exact, so the gathered frame must hash to the same digest
             import hashlib
             out["frame_sha256"] = hashlib.sha256(last.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
             out["frame_view_deg"] = angles[(a.warmup + a.steps - 1) % len(angles)]
-        if a.mode == "render" and a.parity_rays > 0:
+        if a.full and a.mode == "render" and a.parity_rays > 0:
             # ANY world size: the sample is drawn over the whole GATHERED frame — rows other ranks rendered included — re-rendered on this
             # rank's device (bit-equality with the gathered pixels = the exchange moved the right bytes) and teacher-forced against the oracle
             out["parity"] = parity_sample(render, kw, args, K, last, angles[(a.warmup + a.steps - 1) % len(angles)], bm, tex, exp, dev,
                                           n=a.parity_rays)
-        if world == 1 and a.mode == "render" and ARCH == (8, 256, 10, 1024) and (H, W) == (512, 512) and not a.netchunk:
+        if a.full and world == 1 and a.mode == "render" and ARCH == (8, 256, 10, 1024) and (H, W) == (512, 512) and not a.netchunk:
             out["variants"] = {}
             if a.variant_steps > 0:
                 out["variants"]["fine256x8"] = variant_series((8, 256, 8, 256), a.variant_steps, dev, L, bm, tex, exp, K, rays, angles, args)
@@ -703,7 +756,7 @@ def main():
                 out["variants"]["train4096"] = step_variant("train", 4096, a.train_steps, 4, dev, L, K, bm, tex, exp)
             if a.bulk_identities > 0:
                 out["variants"]["bulk256"] = bulk_variant(dev, identities=a.bulk_identities)
-        if world == 1 and a.cpu_rays > 0:
+        if a.full and world == 1 and a.cpu_rays > 0:
             out["cpu_baseline"] = cpu_baseline(a.cpu_rays, backward=(a.mode == "fit"), reps=a.cpu_reps,
                                                tile_reps=a.cpu_tile_reps if (H, W) == (512, 512) else 0)
         print(json.dumps(out), flush=True)

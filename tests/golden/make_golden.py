@@ -749,8 +749,32 @@ def g16_flags():
     save("flags_e2e.npz", o)
 
 
+def g17_ckpt_w64_schema():
+    """What the reference's own reload loop (create_model_condition.py:72-89) requires of a checkpoint of the 8x64 + 10x64 networks:
+    every state-dict key -> shape its modules load strictly, the Adam param-group layout over coarse + fine + ``grad_parameter()``
+    with the shapes of those parameters in order, and the shapes of the expression sigma latents.  Shapes only - no weights."""
+    import json
+    r = mk_renderer(4096, 0)
+    mk = lambda D, W: NeRF(D=D, W=W, input_ch_shapeCodes=50, input_ch_textureCodes=256, input_ch=93, output_ch=5, skips=[4],
+                           input_ch_views=27, use_viewdirs=True)
+    coarse, fine = mk(8, 64), mk(10, 64)
+    grad_vars = list(coarse.parameters()) + list(fine.parameters()) + list(r.grad_parameter())
+    opt = torch.optim.Adam(params=grad_vars, lr=5e-5)
+    sd = lambda m: {k: list(v.shape) for k, v in m.state_dict().items()}
+    out = {"network_fn_state_dict": sd(coarse), "network_fine_state_dict": sd(fine),
+           "network_render_textureEncoder": sd(r.texEncoder), "network_render_idSpecific": sd(r.idSpecificMod),
+           "optimizer_param_group_sizes": [len(g["params"]) for g in opt.state_dict()["param_groups"]],
+           "grad_vars_shapes": [list(p.shape) for p in grad_vars],
+           "expression_latent_codes_sigma": [list(t.shape) for t in r.expCodes_Sigma]}
+    p = os.path.join(HERE, "ckpt_w64_schema.json")
+    with open(p, "w") as f:
+        json.dump(out, f, indent=0)
+    print(f"wrote ckpt_w64_schema.json: {os.path.getsize(p) / 1024:.1f} KiB")
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17"]
     for w in which:
         {"g1": g1_kats, "g2": g2_small, "g3": g3_true, "g4": g4_grads, "g5": g5_render_tex, "g6": g6_schema, "g7": g7_config1, "g8": g8_true_grads, "g9": g9_run_network_kat,
-         "g10": g10_checkpoint, "g11": g11_envelopes, "g12": g12_pose_grads, "g13": g13_ndc, "g14": g14_samplers, "g15": g15_long_rays, "g16": g16_flags}[w]()
+         "g10": g10_checkpoint, "g11": g11_envelopes, "g12": g12_pose_grads, "g13": g13_ndc, "g14": g14_samplers, "g15": g15_long_rays, "g16": g16_flags,
+         "g17": g17_ckpt_w64_schema}[w]()

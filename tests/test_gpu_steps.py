@@ -118,7 +118,7 @@ def test_bench_self_spawns_two_ranks_and_emits_one_contract_json_line():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["MOFA_DIST_BACKEND"] = "gloo"
     j = _run_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--size", "64",
-                   "--arch", "8", "64", "10", "64"], env)
+                   "--arch", "8", "64", "10", "64", "--full"], env)
     for k in _CONTRACT:
         assert k in j, k
     assert j["n_gpus"] == 2 and j["value"] > 0 and j["unit"] == "rays/s" and "cpu_baseline" not in j
@@ -140,7 +140,7 @@ def test_bench_eight_ranks_validate_themselves_and_reproduce_the_one_rank_frame(
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["MOFA_DIST_BACKEND"] = "gloo"
-    common = ["--steps", "2", "--warmup", "1", "--size", "128", "--arch", "8", "64", "10", "512", "--parity-rays", "256"]
+    common = ["--steps", "2", "--warmup", "1", "--size", "128", "--arch", "8", "64", "10", "512", "--parity-rays", "256", "--full"]
     j8 = _run_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8"] + common, env, timeout=1500)
     j1 = _run_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--cpu-rays", "0"] + common, env, timeout=1500)
     for k in _CONTRACT:
@@ -213,13 +213,41 @@ def test_bench_fit_and_train_modes_emit_contract_lines(mode):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     j = _run_json([sys.executable, os.path.join(root, "bench.py"), "--mode", mode, "--steps", "2", "--warmup", "1", "--size", "64",
-                   "--rays", "512", "--arch", "8", "128", "10", "128", "--cpu-rays", "0"], env)
+                   "--rays", "512", "--arch", "8", "128", "10", "128", "--cpu-rays", "0", "--full"], env)
     for k in _CONTRACT:
         assert k in j, k
     assert j["config"]["mode"] == mode and j["scaling"] == "weak" and j["value"] > 0 and j["config"]["rays_per_step"] == 512
     assert j["roofline"]["bound"] == "mfma" and j["roofline"]["achieved"] > 0 and j["roofline"]["launches"] > 0
     kinds = [j["roofline"]["role"] + " " + j["roofline"]["kernel"]] + [o["role"] + " " + o["kernel"] for o in j["roofline"]["other_mfma_kernels"]]
     assert any("BWD" in k for k in kinds) and (mode == "fit" or any("k_wgrad" in k for k in kinds))
+
+
+def test_bench_plain_line_is_lean_and_dumps_the_frame_the_full_line_hashes(tmp_path):
+    """A plain `bench.py` run does only what its headline needs (no roofline, frame digest, parity, variants or CPU baseline), and
+    `--dump-outputs DIR` writes the frame its last timed step returned: float32 rgb / disp / acc whose bytes are the `frame_sha256` a
+    `--full` run reports for the same arguments, and which that run's own dump repeats bit for bit."""
+    import hashlib
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--size", "64",
+           "--arch", "8", "64", "10", "64"]
+    j = _run_json(cmd + ["--dump-outputs", str(tmp_path / "plain")], env)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j, k
+    assert j["steps"] == 2 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0 and j["dtype"] == "f32"
+    assert not {"roofline", "roofline_hbm", "whole_path_tflops", "frame_sha256", "parity", "variants", "cpu_baseline"} & set(j), sorted(j)
+    jf = _run_json(cmd + ["--full", "--parity-rays", "0", "--cpu-rays", "0", "--dump-outputs", str(tmp_path / "full")], env)
+    assert jf["roofline"]["launches"] > 0 and len(jf["frame_sha256"]) == 64
+    got = {n: np.load(tmp_path / "plain" / f"{n}.npy") for n in ("rgb", "disp", "acc")}
+    assert sorted(os.listdir(tmp_path / "plain")) == ["acc.npy", "disp.npy", "rgb.npy"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["rgb"].shape == (64 * 64, 3) and got["disp"].shape == got["acc"].shape == (64 * 64,)
+    frame = np.ascontiguousarray(np.concatenate([got["rgb"], got["disp"][:, None], got["acc"][:, None]], 1))
+    assert hashlib.sha256(frame.tobytes()).hexdigest() == jf["frame_sha256"]
+    for n, v in got.items():
+        np.testing.assert_array_equal(np.load(tmp_path / "full" / f"{n}.npy"), v)
 
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs: the real RCCL (backend nccl) path over xGMI")

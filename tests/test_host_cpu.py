@@ -174,46 +174,33 @@ def test_png_sink_matches_to8b(tmp_path):
         write_png(str(tmp_path / "bad.png"), np.zeros((4, 4), np.uint8))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="build container only: loads the file into the reference's own modules")
 def test_checkpoint_written_here_loads_into_the_reference_modules(tmp_path):
-    """(f4) `save_checkpoint` output is consumed by the REFERENCE's modules with strict `load_state_dict` and its own
-    reload loop (create_model_condition.py:72-89) — run in a subprocess because importing the reference needs process-wide
-    shims (stub imageio / cv2, Tensor.cuda = identity)."""
-    import subprocess
-    import sys
+    """(f4) `save_checkpoint` output satisfies what the REFERENCE's own reload loop (create_model_condition.py:72-89) asks of it:
+    strict `load_state_dict` of both networks, the texture encoder and the StyleModule (every key, no extra one, same shapes), the
+    Adam state over coarse + fine + `grad_parameter()` (same group sizes; any saved moment has its parameter's shape), the expression
+    sigma latents copied one to one, and the step counter.  What the reference's modules require is recorded from them in
+    tests/golden/ckpt_w64_schema.json (tests/golden/make_golden.py g17)."""
+    with open(os.path.join(HERE, "golden", "ckpt_w64_schema.json")) as f:
+        ref = json.load(f)
     a = factory.default_args(device="cpu", netwidth=64, netwidth_fine=64, basedir=str(tmp_path), expname="rt", no_reload=True)
     kw, _, _, grad_vars, opt, _, render = factory.create_nerf(a)
     kw["network_fn"].load_state_dict(synth.nerf_state(8, 64, 5, "coarse"))
     kw["network_fine"].load_state_dict(synth.nerf_state(10, 64, 5, "fine"))
     path = factory.save_checkpoint(str(tmp_path / "rt" / "000042.tar"), 42, kw, render, opt)
-    code = f"""
-import sys, types, torch
-sys.path.insert(0, '/root/reference')
-for m in ('imageio', 'cv2'):
-    sys.modules[m] = types.ModuleType(m)
-torch.Tensor.cuda = lambda self, *a, **k: self
-from models import render_class
-from models.model import NeRF, get_embedder
-ck = torch.load({path!r}, map_location='cpu', weights_only=False)
-mk = lambda D, W: NeRF(D=D, W=W, input_ch_shapeCodes=50, input_ch_textureCodes=256, input_ch=93, output_ch=5, skips=[4],
-                       input_ch_views=27, use_viewdirs=True)
-coarse, fine = mk(8, 64), mk(10, 64)
-r = render_class.myRenderer(embed_fn=get_embedder(10, 0)[0], embeddirs_fn=get_embedder(4, 0)[0], netchunk=4096, uvCodesLen=256,
-                            expCodesLen=30)
-opt = torch.optim.Adam(params=list(coarse.parameters()) + list(fine.parameters()) + list(r.grad_parameter()), lr=5e-5)
-opt.load_state_dict(ck['optimizer_state_dict'])
-coarse.load_state_dict(ck['network_fn_state_dict'])
-fine.load_state_dict(ck['network_fine_state_dict'])
-r.texEncoder.load_state_dict(ck['network_render_textureEncoder'])
-r.idSpecificMod.load_state_dict(ck['network_render_idSpecific'])
-for latent, saved in zip(r.expCodes_Sigma, ck['expression_latent_codes_sigma']):
-    latent.data[:] = saved[:].detach().clone()
-assert ck['global_step'] == 42
-print('REFERENCE_LOADED', float(fine.rgb_linear.weight.sum()))
-"""
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "REFERENCE_LOADED" in out.stdout, out.stderr[-1500:]
-    got = float(out.stdout.split("REFERENCE_LOADED")[1].split()[0])
+    ck = torch.load(path, map_location="cpu", weights_only=False)
+    for name in ("network_fn_state_dict", "network_fine_state_dict", "network_render_textureEncoder", "network_render_idSpecific"):
+        got = _shapes(ck[name])
+        assert sorted(got) == sorted(ref[name]), (name, sorted(set(got) ^ set(ref[name])))
+        assert got == ref[name], name
+    saved = ck["optimizer_state_dict"]
+    assert [len(g["params"]) for g in saved["param_groups"]] == ref["optimizer_param_group_sizes"]
+    order = [i for g in saved["param_groups"] for i in g["params"]]
+    for i, st in saved["state"].items():
+        shape = ref["grad_vars_shapes"][order.index(i)]
+        assert all(list(v.shape) == shape for k, v in st.items() if k != "step"), i
+    assert [list(t.shape) for t in ck["expression_latent_codes_sigma"]] == ref["expression_latent_codes_sigma"]
+    assert ck["global_step"] == 42
+    got = float(ck["network_fine_state_dict"]["rgb_linear.weight"].sum())
     assert abs(got - float(kw["network_fine"].rgb_linear.weight.detach().sum())) < 1e-5
 
 
@@ -278,6 +265,32 @@ def test_bench_roofline_hbm_prices_the_ray_kernels_against_the_hbm_peak():
     assert stale[0]["traffic"] is None and "null" in stale[0]["traffic_source"]
     dom, mf = bench.roofline_of(ms, launches, work, dt=1.0)                       # the MFMA roofline never picks a ray kernel
     assert dom == 5
+
+
+def test_bench_dump_outputs_writes_float32_and_samples_past_the_cap(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: one float32 .npy per array; past MAX_DUMP_BYTES in all, the same seeded rows of every array (their
+    numbers in sample_rows.npy, float64) and nothing beyond the cap."""
+    import bench
+    assert bench.MAX_DUMP_BYTES == 64 * 2 ** 20
+    g = torch.Generator().manual_seed(1)
+    rgb, disp = torch.rand(1000, 3, generator=g, dtype=torch.float64), torch.rand(1000, generator=g)
+    bench.dump_outputs(str(tmp_path / "a"), {"rgb": rgb, "disp": disp})
+    assert sorted(os.listdir(tmp_path / "a")) == ["disp.npy", "rgb.npy"]
+    a = np.load(tmp_path / "a" / "rgb.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, rgb.float().numpy())
+    monkeypatch.setattr(bench, "MAX_DUMP_BYTES", 8192)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"rgb": rgb, "disp": disp})
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["disp.npy", "rgb.npy", "sample_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= 8192
+    rows = np.load(tmp_path / "b" / "sample_rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    idx = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "b" / "rgb.npy"), rgb.float().numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "b" / "disp.npy"), disp.numpy()[idx])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
 
 
 def test_committed_traffic_profiles_were_taken_on_the_committed_kernel_sources():

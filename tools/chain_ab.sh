@@ -8,7 +8,7 @@ tag=${1:-r05}; shift
 export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 out=gpurun_out/$tag/chain_ab; mkdir -p $out
-quick="--steps 3 --warmup 1 --cpu-rays 0 --variant-steps 0 --fit-steps 0 --train-steps 0 --parity-rays 0"
+quick="--full --steps 3 --warmup 1 --cpu-rays 0 --variant-steps 0 --fit-steps 0 --train-steps 0 --parity-rays 0"   # --full: roofline.frac below
 run() { if [ "$1" = base ]; then shift; "$@"; else a=$1; shift; env "$a" "$@"; fi; }
 for rep in 1 2; do
   for arm in "$@"; do

@@ -36,8 +36,10 @@ db=$(find /tmp/prof_rccl -name '*.db' | head -1)
 [ -n "$db" ] && python tools/rocpd_stats.py "$db" gpurun_out/$tag/kernel_stats_rccl_world1.md "rocprofv3 --kernel-trace --stats -- python tools/rccl_world1.py"
 # the round's plain bench lines (no profiler attached), with the PMC traffic of THIS build next to the live roofline figure
 cp gpurun_out/$tag/hbm_traffic.json profiles/hbm_traffic.json
-python bench.py > gpurun_out/$tag/bench_n1.json 2> gpurun_out/$tag/bench_n1.err
-python bench.py --mode fit > gpurun_out/$tag/bench_fit_n1.json 2> gpurun_out/$tag/bench_fit_n1.err
-python bench.py --mode train > gpurun_out/$tag/bench_train_n1.json 2> gpurun_out/$tag/bench_train_n1.err
-python bench.py --arch 8 256 8 256 --cpu-rays 0 > gpurun_out/$tag/bench_n1_variant_fine256x8.json 2> /dev/null
+# (--full: the roofline, parity, variants and cpu_baseline figures; the lines go to $rec, BENCH_OUT/<tag>, default bench_out/<tag>)
+rec=${BENCH_OUT:-bench_out}/$tag; mkdir -p $rec
+python bench.py --full > $rec/bench_n1.json 2> $rec/bench_n1.err
+python bench.py --full --mode fit > $rec/bench_fit_n1.json 2> $rec/bench_fit_n1.err
+python bench.py --full --mode train > $rec/bench_train_n1.json 2> $rec/bench_train_n1.err
+python bench.py --full --arch 8 256 8 256 --cpu-rays 0 > $rec/bench_n1_variant_fine256x8.json 2> /dev/null
 ls -la gpurun_out/$tag

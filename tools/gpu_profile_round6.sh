@@ -29,12 +29,14 @@ bash tools/gpu_profile_rays.sh $tag > /dev/null 2>&1
 python tools/make_traffic_rays_json.py gpurun_out/$tag gpurun_out/$tag/hbm_traffic_rays.json > /dev/null 2> gpurun_out/$tag/hbm_traffic_rays.err
 cp gpurun_out/$tag/hbm_traffic_chain.json gpurun_out/$tag/hbm_traffic_rays.json profiles/ 2>/dev/null
 python tools/kernel_resources.py mofanerf_amd/libmofanerf_hip.so gpurun_out/$tag/kernel_resources.md > /dev/null
-python bench.py > gpurun_out/$tag/bench_n1.json 2> gpurun_out/$tag/bench_n1.err
-python bench.py --mode fit > gpurun_out/$tag/bench_fit_n1.json 2> gpurun_out/$tag/bench_fit_n1.err
-python bench.py --mode train > gpurun_out/$tag/bench_train_n1.json 2> gpurun_out/$tag/bench_train_n1.err
-MOFA_CHAIN_TRAIN=1 python bench.py --mode train > gpurun_out/$tag/bench_train_n1_chain_train.json 2> gpurun_out/$tag/bench_train_n1_chain_train.err
+# (--full: the roofline, parity, variants and cpu_baseline figures; the lines go to $rec, BENCH_OUT/<tag>, default bench_out/<tag>)
+rec=${BENCH_OUT:-bench_out}/$tag; mkdir -p $rec
+python bench.py --full > $rec/bench_n1.json 2> $rec/bench_n1.err
+python bench.py --full --mode fit > $rec/bench_fit_n1.json 2> $rec/bench_fit_n1.err
+python bench.py --full --mode train > $rec/bench_train_n1.json 2> $rec/bench_train_n1.err
+MOFA_CHAIN_TRAIN=1 python bench.py --full --mode train > $rec/bench_train_n1_chain_train.json 2> $rec/bench_train_n1_chain_train.err
 t0=$SECONDS
-python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/$tag/bench_n1_steps20_warmup5.json 2> gpurun_out/$tag/bench_n1_steps20_warmup5.err
-echo "wall clock of the whole command: $((SECONDS - t0)) s" >> gpurun_out/$tag/bench_n1_steps20_warmup5.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $rec/bench_n1_steps20_warmup5.json 2> $rec/bench_n1_steps20_warmup5.err
+echo "wall clock of the whole command: $((SECONDS - t0)) s" >> $rec/bench_n1_steps20_warmup5.err
 [ "${SKIP_STRESS:-0}" = 1 ] || timeout 1500 python tools/stress_chain.py ${STRESS_SCALE:-0.5} > gpurun_out/$tag/stress_chain.txt 2>&1
 ls -la gpurun_out/$tag | head -60
