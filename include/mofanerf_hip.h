@@ -170,6 +170,38 @@ int mofa_net_forward(MofaNetShape s, const float* packed, const float* folded, c
                      const float* view_b, const float* rays_o, const float* rays_d, const float* z, int64_t z_row_stride,
                      const float* pts, const float* viewdirs, int64_t n_rays, int32_t S, float* workspace,
                      float* raw_out, float* tape, uint64_t* mask_tape, const float* view_bias_rows, uint32_t* verdict, void* stream);
+/* Density only — the geometry half of the network: sigma_out[n] = the pre-ReLU alpha head at explicit points pts [n,3], the SAME bits as
+ * raw_out[..., 3] of mofa_net_forward on those points, whatever view directions and texture code that call had.  Density depends on the
+ * point, the shape code and the expression code only (model.py:121-128): the launch stops after the linear_BiM_xyz stack — no texture
+ * stack, no view layer, no rgb head — on the same layer kernels, chained or per layer by the same choice (never the persistent kernel:
+ * widths <= 256 take the per-layer launches, bit-identical).  `folded` from mofa_net_fold (the texture code is not read: zeros do).
+ *   workspace: mofa_net_workspace_floats(s, n_points, 1) floats.  verdict: as for mofa_net_forward (a chained launch that ended
+ *   incomplete leaves NaN in sigma_out and raises the words). */
+int mofa_net_density(MofaNetShape s, const float* packed, const float* folded, const float* pts, int64_t n_points, float* workspace,
+                     float* sigma_out, uint32_t* verdict, void* stream);
+
+/* ---- geometry export: grid points and the iso-surface of a density grid ---------------------------------------------------------
+ * Grid sample points: pts[n,3] for the flat indices first .. first+n-1 of an nx x ny x nz grid, idx = (i*ny + j)*nz + k (C order, z
+ * fastest); x = lo_x + (float)i * step_x with the multiply and the add rounded separately (likewise y, z).  lo / step: HOST arrays. */
+int mofa_grid_points(int64_t nx, int64_t ny, int64_t nz, const float lo[3], const float step[3], int64_t first, int64_t n, float* pts,
+                     void* stream);
+/* Marching tetrahedra on the Freudenthal split of grid [nx,ny,nz] (the sample at idx above): a watertight, consistently oriented
+ * triangle mesh of {sigma >= level} (NaN counts as outside), normals (v1-v0) x (v2-v0) toward lower sigma.  Each cell (i,j,k) is
+ * 6 tets {0, e_a, e_a+e_b, e_a+e_b+e_c}, one per axis permutation (a,b,c) in lexicographic order; every tet edge is a lattice edge
+ * in one of the directions +x, +y, +z, +x+y, +x+z, +y+z, +x+y+z, owned by its lower endpoint: edge_id = 7 idx + dir.  A vertex sits on
+ * every edge whose ends differ, at t = (level - s_a) / (s_b - s_a), p = p_a + t (p_b - p_a) (a = the lower endpoint, p from the
+ * mofa_grid_points formula, every operation separately rounded).  Vertices are numbered in increasing edge_id, faces ordered by cell,
+ * tet, triangle: no atomics, the same bits on every run.  Two phases, because the caller sizes the outputs:
+ *   mofa_iso_count  writes counts[0] = V, counts[1] = F (int64, DEVICE) and keeps the edge / cell scans in `workspace`;
+ *   mofa_iso_emit   with the SAME grid, level and workspace afterwards: verts [V,3] (float), faces [F,3] (int32 vertex ids).
+ * The grid needs >= 2 samples per axis and 7 nx ny nz < 2^31; the level must be finite; emit needs finite lo and step > 0 (host arrays).
+ * A result with V or F above 2^31 - 1 is refused: emit then writes nothing (the caller sees it in the counts).  V = F = 0 is a result.
+ * A non-finite sample next to a crossing gives non-finite vertices: check the grid first. */
+size_t mofa_iso_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);   /* 0 for a grid that is refused */
+int mofa_iso_count(const float* grid, int64_t nx, int64_t ny, int64_t nz, float level, void* workspace, int64_t* counts, void* stream);
+int mofa_iso_emit(const float* grid, int64_t nx, int64_t ny, int64_t nz, const float lo[3], const float step[3], float level, void* workspace,
+                  float* verts, int32_t* faces, void* stream);
+
 /* ---- backward (run_fit.py:305-313 photometric fitting, run_train.py:333-357 training) -----------------------
  * Backward of mofa_net_forward given d_raw [n_rays,S,4] and the tape (fp32, or mask-only when d_weights == NULL) of that forward:
  *   d_folded  [mofa_net_folded_floats]: gradient w.r.t. every folded bias (sum over points of the ReLU-masked

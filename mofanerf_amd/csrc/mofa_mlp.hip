@@ -19,6 +19,8 @@ namespace mofa {
 namespace {
 
 // ---- heads: sigma = sigmaCodes . w + b (model.py:130), rgb = v . W3 + b3 (model.py:134) ---------
+// LD: floats per output row — 4 for raw [n,4] (column raw_off + o), 1 for the density form's dense sigma [n] (same summation order)
+template <int LD>
 __global__ __launch_bounds__(256) void k_head(const float* __restrict__ x, int kp, long long m_padded,
                                               const float* __restrict__ w, const float* __restrict__ b, int n_out,
                                               float* __restrict__ raw, int raw_off, long long n_points) {
@@ -49,7 +51,7 @@ __global__ __launch_bounds__(256) void k_head(const float* __restrict__ x, int k
             }
         }
     }
-    for (int o = 0; o < n_out; ++o) raw[m * 4 + raw_off + o] = acc[o] + b[o];
+    for (int o = 0; o < n_out; ++o) raw[m * LD + raw_off + o] = acc[o] + b[o];
 }
 
 // ---- per-ray bias of the view layer: b + W[:, :27] @ PE(viewdir)  (model.py:133, render_class.py:88-90)
@@ -1598,8 +1600,19 @@ int mofa_head_forward(const float* x, int32_t k_padded, int64_t m_padded, const 
     MOFA_REQUIRE(k_padded % 16 == 0 && n_out >= 1 && n_out <= 4 && raw_off >= 0 && raw_off + n_out <= 4 &&
                      n_points <= m_padded,
                  "head_forward: bad shape");
-    hipLaunchKernelGGL(k_head, dim3(blocks_for(n_points)), dim3(256), 0, (hipStream_t)stream, x, k_padded / 16,
+    hipLaunchKernelGGL(k_head<4>, dim3(blocks_for(n_points)), dim3(256), 0, (hipStream_t)stream, x, k_padded / 16,
                        (long long)m_padded, w_dense, b, n_out, raw, raw_off, (long long)n_points);
+    return check_launch("k_head");
+}
+
+// internal (used by mofa_net.hip): the alpha head of the density form — out[m] = sigmaCodes[m] . w + b, the value mofa_head_forward
+// writes into raw[m][3], bit for bit
+int mofa_internal_head_dense(const float* x, int32_t k_padded, int64_t m_padded, const float* w_dense, const float* b, float* out,
+                             int64_t n_points, void* stream) {
+    MOFA_REQUIRE(x && w_dense && b && out, "head_dense: null pointer");
+    MOFA_REQUIRE(k_padded % 16 == 0 && n_points > 0 && n_points <= m_padded, "head_dense: bad shape");
+    hipLaunchKernelGGL(k_head<1>, dim3(blocks_for(n_points)), dim3(256), 0, (hipStream_t)stream, x, k_padded / 16,
+                       (long long)m_padded, w_dense, b, 1, out, 0, (long long)n_points);
     return check_launch("k_head");
 }
 

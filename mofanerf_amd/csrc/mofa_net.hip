@@ -39,6 +39,8 @@ int mofa_internal_chain_selfcheck(void* stream, int* ok, char* why, size_t why_l
 int mofa_internal_chain_train_launch(const mofa::ChainStep* steps, int n_steps, long long m_padded, long long n_points, unsigned* state,
                                      long long* tiles_out, void* stream);
 int mofa_internal_chain_poison(const unsigned* state, long long tiles, float* const* ptrs, const long long* sizes, int count, void* stream);
+int mofa_internal_head_dense(const float* x, int32_t k_padded, int64_t m_padded, const float* w_dense, const float* b, float* out,
+                              int64_t n_points, void* stream);
 int mofa_internal_wgrad_reduce(const float* partial, int splits, int n_padded, int k_padded, int n_out, int ncols, float* dst, int ld,
                                int col0, float* bias_out, void* stream);
 }
@@ -388,18 +390,23 @@ int mofa_net_pack_t(MofaNetShape s, const float* const* weights, float* packed_t
 
 // force_chain: -1 = by configuration + census (every caller but the self-check); 0 = the per-layer launches, 1 = the chained launch —
 // whatever MOFA_* says and whatever the census found (mofa_device_init's self-check runs both forms on the same inputs)
+// sigma_out != NULL: the DENSITY form (mofa_net_density) — the step list stops after the shape stack (sigmaCodes), there is no texture
+// stack, no view bias, no view layer and no rgb head, and the alpha head writes sigma_out[n] densely instead of raw_out[n][3].  Explicit
+// points only (n_rays = n_points, S = 1), no tape, never the persistent kernel: the chained or per-layer launches of the same tiles.
 static int net_forward(MofaNetShape s, const float* packed, const float* folded, const float* view_w,
                        const float* view_b, const float* rays_o, const float* rays_d, const float* z, int64_t z_row_stride,
                        const float* pts, const float* viewdirs, int64_t n_rays, int32_t S, float* workspace,
                        float* raw_out, float* tape, uint64_t* mask_tape, const float* view_bias_rows, uint32_t* verdict, void* stream,
-                       int force_chain) {
+                       int force_chain, float* sigma_out = nullptr) {
+    const bool density = sigma_out != nullptr;
     MOFA_REQUIRE(shape_ok(s), "net_forward: unsupported shape " MOFA_SHAPE_FMT, MOFA_SHAPE_ARGS(s));
-    MOFA_REQUIRE(packed && folded && workspace && raw_out, "net_forward: null pointer");
+    MOFA_REQUIRE(packed && folded && workspace && (raw_out || density), "net_forward: null pointer");
     MOFA_REQUIRE(!(tape && mask_tape), "net_forward: give the fp32 tape OR the mask-only tape, not both");
-    MOFA_REQUIRE(view_bias_rows || (view_w && view_b && viewdirs),
+    MOFA_REQUIRE(density || view_bias_rows || (view_w && view_b && viewdirs),
                  "net_forward: need view_bias_rows or (view_w, view_b, viewdirs)");
     MOFA_REQUIRE(n_rays > 0 && S > 0, "net_forward: n_rays=%lld S=%d", (long long)n_rays, S);
     MOFA_REQUIRE(pts || (rays_o && rays_d && z), "net_forward: need pts or (rays_o, rays_d, z)");
+    MOFA_REQUIRE(!density || (pts && S == 1 && !tape && !mask_tape && !raw_out), "net_forward: bad density call");
     const Plan p = make_plan(s);
     const int64_t M = n_rays * S, Mp = round_up(M, kRowTile);
     const size_t act = (size_t)Mp * p.Wp;
@@ -452,14 +459,17 @@ static int net_forward(MofaNetShape s, const float* packed, const float* folded,
         return const_cast<float*>(cur);
     };
     float* sigma = cond(p.bim0, p.bim_skip, xyz, bufB, t0, t1);
-    float* rgbc = cond(p.uv0, p.uv_skip, sigma, bufA, t0, t1);  // without a tape rgbCodes reuses xyz_code's buffer
-    float* v = slot(p.view, t0);
-    steps.push_back({p.view, rgbc, nullptr, v});
+    float* v = nullptr;
+    if (!density) {                                                 // (density: sigmaCodes is all the alpha head reads)
+        float* rgbc = cond(p.uv0, p.uv_skip, sigma, bufA, t0, t1);  // without a tape rgbCodes reuses xyz_code's buffer
+        v = slot(p.view, t0);
+        steps.push_back({p.view, rgbc, nullptr, v});
+    }
 
     int rc;
     unsigned* chain_state = nullptr;      // set when the chained launch ran: its status words are verified behind the heads
     long long chain_tiles = 0;
-    if (!view_bias_rows) {
+    if (!density && !view_bias_rows) {
         // per-ray bias b + W[:, :27] @ PE(viewdir) from the ORIGINAL (unpacked) view-layer tensors
         const Layer& l = p.L[p.view];
         MOFA_TRY(mofa_view_bias(viewdirs, n_rays, s.pe_view_freqs, view_w, l.n_out, l.ld, view_b, vbias, l.n_padded, stream));
@@ -483,7 +493,7 @@ static int net_forward(MofaNetShape s, const float* packed, const float* folded,
     //      chained launch over the tiles of every layer (inference), else one launch per layer.  MOFA_FUSED=0/1 and MOFA_CHAIN=0 override
     //      the choice (tests / A-B).
     const Config& cfg = config();
-    const bool fused = force_chain < 0 && (cfg.fused >= 0 ? cfg.fused == 1 : (p.Wp <= 256 && Mp / kRowTile >= 128));
+    const bool fused = !density && force_chain < 0 && (cfg.fused >= 0 ? cfg.fused == 1 : (p.Wp <= 256 && Mp / kRowTile >= 128));
     if (fused) {
         const float* arena = tape ? tape : workspace;
         const int n = (int)steps.size();
@@ -527,7 +537,7 @@ static int net_forward(MofaNetShape s, const float* packed, const float* folded,
             c.n_padded = l.n_padded, c.bias_row_div = view ? S : 0, c.flags = 1;
             cs[i] = c;
         }
-        chain_state = (unsigned*)(vbias + (size_t)n_rays * p.Hp + 64);
+        chain_state = (unsigned*)(vbias + (size_t)(density ? 1 : n_rays) * p.Hp + 64);   // (a density workspace holds one bias row)
         MOFA_TRY(mofa_internal_chain_launch(mask_tape ? kChainForwardMask : kChainForward, cs.data(), (int)cs.size(), Mp, n_rays, chain_state,
                                             &chain_tiles, stream));
         if (mask_tape) MOFA_TRY(mofa_internal_mask_pack(v, (long long)Mp * p.L[p.view].n_padded, mbits + mword(p.view), stream));
@@ -558,6 +568,12 @@ static int net_forward(MofaNetShape s, const float* packed, const float* folded,
         }
     }
     // ---- heads: sigma from sigmaCodes, rgb from the view layer's output ------------------------------------------
+    if (density) {
+        const Layer& l = p.L[p.alpha];
+        MOFA_TRY(mofa_internal_head_dense(sigma, l.k_padded[0], Mp, packed + l.packed_off, folded + l.folded_off, sigma_out, M, stream));
+        if (chain_state) MOFA_TRY(mofa_internal_chain_verify(chain_state, chain_tiles, verdict, sigma_out, M, nullptr, 0, nullptr, 0, nullptr, 0, stream));
+        return MOFA_OK;
+    }
     {
         const Layer& l = p.L[p.alpha];
         auto head = mofa_head_forward;
@@ -576,6 +592,15 @@ int mofa_net_forward(MofaNetShape s, const float* packed, const float* folded, c
                      float* raw_out, float* tape, uint64_t* mask_tape, const float* view_bias_rows, uint32_t* verdict, void* stream) {
     return net_forward(s, packed, folded, view_w, view_b, rays_o, rays_d, z, z_row_stride, pts, viewdirs, n_rays, S, workspace, raw_out, tape,
                        mask_tape, view_bias_rows, verdict, stream, -1);
+}
+
+int mofa_net_density(MofaNetShape s, const float* packed, const float* folded, const float* pts, int64_t n_points, float* workspace,
+                     float* sigma_out, uint32_t* verdict, void* stream) {
+    MOFA_REQUIRE(shape_ok(s), "net_density: unsupported shape " MOFA_SHAPE_FMT, MOFA_SHAPE_ARGS(s));
+    MOFA_REQUIRE(packed && folded && pts && workspace && sigma_out, "net_density: null pointer");
+    MOFA_REQUIRE(n_points > 0 && n_points / kRowTile < (1 << 24), "net_density: n_points=%lld", (long long)n_points);
+    return net_forward(s, packed, folded, nullptr, nullptr, nullptr, nullptr, nullptr, 0, pts, nullptr, n_points, 1, workspace, nullptr, nullptr,
+                       nullptr, nullptr, verdict, stream, -1, sigma_out);
 }
 
 // ---- the chained launch's self-check (mofa_device_init) ---------------------------------------------------------

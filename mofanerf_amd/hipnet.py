@@ -446,3 +446,15 @@ class HipNet:
                                            self.verdict_ptr(viewdirs.device), lib.stream()), "mofa_net_forward")
         self.snapshot_verdict()
         return raw_out
+
+    def density_points(self, pts, sigma_out: torch.Tensor, folded: Optional[torch.Tensor] = None):
+        """sigma_out[n] = the pre-ReLU density of the points ``pts [n,3]`` — ``raw[..., 3]`` of :meth:`forward_points` on the same points,
+        bit for bit, without the texture stack, the view layer or the rgb head (``mofa_net_density``).  Inference only."""
+        n = int(pts.shape[0])
+        ws = self.workspace(n, 1, pts.device)
+        self.check_verdict()
+        lib.check(self._L.mofa_net_density(self.shape, lib.ptr(self.packed()), lib.ptr(folded if folded is not None else self._folded),
+                                           lib.ptr(pts), n, lib.ptr(ws), lib.ptr(sigma_out), self.verdict_ptr(pts.device), lib.stream()),
+                  "mofa_net_density")
+        self.snapshot_verdict()
+        return sigma_out

@@ -53,6 +53,11 @@ SIGNATURES = {
     "mofa_net_fold": (C.c_int, [NetShape, C.POINTER(_fp), C.POINTER(_fp), _fp, _fp, _fp, _fp, _fp]),
     "mofa_net_forward": (C.c_int, [NetShape, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _fp, _fp, _i64, _i32, _fp, _fp,
                                    _fp, _fp, _fp, _fp, _fp]),
+    "mofa_net_density": (C.c_int, [NetShape, _fp, _fp, _fp, _i64, _fp, _fp, _fp, _fp]),
+    "mofa_grid_points": (C.c_int, [_i64, _i64, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), _i64, _i64, _fp, _fp]),
+    "mofa_iso_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "mofa_iso_count": (C.c_int, [_fp, _i64, _i64, _i64, C.c_float, _fp, _fp, _fp]),
+    "mofa_iso_emit": (C.c_int, [_fp, _i64, _i64, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _fp, _fp, _fp, _fp]),
     "mofa_net_packed_t_floats": (_sz, [NetShape]),
     "mofa_net_tape_floats": (_sz, [NetShape, _i64]),
     "mofa_net_mask_tape_words": (_sz, [NetShape, _i64]),

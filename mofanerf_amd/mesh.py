@@ -1,0 +1,158 @@
+"""Geometry export: the grid of a density query, the iso-surface of a density grid on the GPU (``mofa_iso_count`` / ``mofa_iso_emit``,
+marching tetrahedra on the Freudenthal split) and a binary PLY writer / reader.
+
+``Renderer.query_density`` and ``Renderer.extract_mesh`` are the user-facing entry points; this module holds the pieces they share.
+The mesh is watertight and consistently oriented (normals toward lower density); vertices and faces come out in a fixed order with
+no atomics, so the same grid gives the same bytes every time.  CPU tensors raise ``MofaError``: there is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import lib
+
+
+def grid_spec(bounds, resolution) -> Tuple[Tuple[int, int, int], np.ndarray, np.ndarray]:
+    """``bounds = ((x0,y0,z0), (x1,y1,z1))``, ``resolution = (nx,ny,nz)`` -> (resolution, lo, step): ``step = (hi - lo) / (n - 1)`` in
+    float32 on the host.  Every axis needs at least 2 samples and hi > lo."""
+    lo, hi = (np.asarray(b, dtype=np.float32).reshape(3) for b in bounds)
+    res = tuple(int(n) for n in resolution)
+    if len(res) != 3 or min(res) < 2:
+        raise lib.MofaError(f"resolution {resolution}: want three axes of at least 2 samples")
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi > lo).all()):
+        raise lib.MofaError(f"bounds {bounds}: want finite (x0, y0, z0) < (x1, y1, z1)")
+    step = ((hi - lo) / (np.asarray(res, dtype=np.float32) - np.float32(1))).astype(np.float32)
+    return res, lo, step
+
+
+def _f3(v) -> C.Array:
+    a = np.asarray(v, dtype=np.float32).reshape(3)
+    return (C.c_float * 3)(*[float(x) for x in a])
+
+
+def grid_points(resolution, lo, step, first: int, n: int, out: torch.Tensor) -> torch.Tensor:
+    """out[n,3] = the sample points ``first .. first+n-1`` of the grid (``mofa_grid_points``: idx = (i*ny + j)*nz + k,
+    x = lo_x + (float)i * step_x, separately rounded)."""
+    nx, ny, nz = resolution
+    lib.check(lib.load().mofa_grid_points(nx, ny, nz, _f3(lo), _f3(step), int(first), int(n), lib.ptr(out), lib.stream()),
+              "mofa_grid_points")
+    return out
+
+
+def iso_surface(grid: torch.Tensor, level: float, lo, step) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Triangle mesh of ``{grid >= level}`` for a density grid ``[nx,ny,nz]`` whose sample (i,j,k) sits at lo + (i,j,k) * step:
+    ``verts [V,3] float32``, ``faces [F,3] int32`` on the grid's device.  Count, one host read of (V, F), emit.  The grid must be
+    finite (a non-finite sample next to the surface has no position)."""
+    if grid.dim() != 3:
+        raise lib.MofaError(f"iso_surface: want a [nx,ny,nz] grid, got {tuple(grid.shape)}")
+    level = float(level)
+    if not np.isfinite(level):
+        raise lib.MofaError(f"iso_surface: the level must be finite (got {level})")
+    g = grid.detach()
+    lib.ptr(g)                                            # (device / dtype / layout check)
+    if not bool(torch.isfinite(g).all()):
+        raise lib.MofaError("iso_surface: the density grid holds non-finite values")
+    nx, ny, nz = (int(v) for v in g.shape)
+    L = lib.load()
+    nbytes = L.mofa_iso_workspace_bytes(nx, ny, nz)
+    if nbytes == 0:
+        raise lib.MofaError(f"iso_surface: grid {nx} x {ny} x {nz} is refused (>= 2 samples per axis, 7 nx ny nz < 2^31)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
+    counts = torch.empty(2, dtype=torch.int64, device=g.device)
+    lib.check(L.mofa_iso_count(lib.ptr(g), nx, ny, nz, level, ws.data_ptr(), counts.data_ptr(), lib.stream()), "mofa_iso_count")
+    V, F = (int(v) for v in counts.cpu())
+    if V > 2 ** 31 - 1 or F > 2 ** 31 - 1:
+        raise lib.MofaError(f"iso_surface: {V} vertices / {F} faces exceed the int32 face indices (2^31 - 1)")
+    verts = torch.empty(V, 3, dtype=torch.float32, device=g.device)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=g.device)
+    if V and F:
+        lib.check(L.mofa_iso_emit(lib.ptr(g), nx, ny, nz, _f3(lo), _f3(step), level, ws.data_ptr(), lib.ptr(verts), faces.data_ptr(),
+                                  lib.stream()), "mofa_iso_emit")
+    return verts, faces
+
+
+def vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """Area-weighted unit vertex normals (the sum of the adjacent faces' cross products, normalised); a vertex whose faces all have
+    zero area gets (0, 0, 0)."""
+    f = faces.long()
+    v0, v1, v2 = verts[f[:, 0]], verts[f[:, 1]], verts[f[:, 2]]
+    fn = torch.linalg.cross(v1 - v0, v2 - v0)
+    n = torch.zeros_like(verts)
+    for c in range(3):
+        n.index_add_(0, f[:, c], fn)
+    return torch.nn.functional.normalize(n, dim=-1)
+
+
+def to8b(x) -> np.ndarray:
+    """The reference's quantisation (tools/run_nerf_helpers.py:12): ``(255 * clip(x, 0, 1))`` truncated to uint8."""
+    return (255 * np.clip(np.asarray(x, dtype=np.float32), 0, 1)).astype(np.uint8)
+
+
+def _host(t) -> np.ndarray:
+    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+
+
+def write_ply(path: str, verts, faces, colors=None) -> None:
+    """Binary little-endian PLY: ``float x, y, z`` (+ ``uchar red, green, blue`` from ``colors`` in [0,1] through ``to8b``) per vertex,
+    ``list uchar int vertex_indices`` per face."""
+    v = np.ascontiguousarray(_host(verts), dtype=np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(_host(faces), dtype=np.int32).reshape(-1, 3)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    props = "property float x\nproperty float y\nproperty float z\n"
+    if colors is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    vrec = np.empty(len(v), dtype=fields)
+    vrec["x"], vrec["y"], vrec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colors is not None:
+        c = to8b(_host(colors)).reshape(-1, 3)
+        if len(c) != len(v):
+            raise ValueError(f"{len(c)} colours for {len(v)} vertices")
+        vrec["red"], vrec["green"], vrec["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    frec = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    frec["n"], frec["i"] = 3, f
+    header = (f"ply\nformat binary_little_endian 1.0\nelement vertex {len(v)}\n{props}"
+              f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(vrec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+    """Read what :func:`write_ply` writes: ``(verts [V,3] float32, faces [F,3] int32, colors [V,3] uint8 or None)``."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").splitlines()
+    if lines[:2] != ["ply", "format binary_little_endian 1.0"]:
+        raise ValueError(f"{path}: not a binary little-endian PLY")
+    n_v = n_f = 0
+    vprops = []
+    element = None
+    for ln in lines[2:]:
+        w = ln.split()
+        if w[0] == "element":
+            element = w[1]
+            if element == "vertex":
+                n_v = int(w[2])
+            elif element == "face":
+                n_f = int(w[2])
+        elif w[0] == "property" and element == "vertex":
+            vprops.append(w[2])
+    types = {"x": "<f4", "y": "<f4", "z": "<f4", "red": "u1", "green": "u1", "blue": "u1"}
+    vdt = np.dtype([(p, types[p]) for p in vprops])
+    vrec = np.frombuffer(data, dtype=vdt, count=n_v, offset=end)
+    frec = np.frombuffer(data, dtype=[("n", "u1"), ("i", "<i4", (3,))], count=n_f, offset=end + n_v * vdt.itemsize)
+    if n_f and not (frec["n"] == 3).all():
+        raise ValueError(f"{path}: faces that are not triangles")
+    verts = np.stack([vrec["x"], vrec["y"], vrec["z"]], -1).astype(np.float32).reshape(-1, 3)
+    colors = np.stack([vrec["red"], vrec["green"], vrec["blue"]], -1).reshape(-1, 3) if "red" in vprops else None
+    return verts, np.ascontiguousarray(frec["i"]).astype(np.int32).reshape(-1, 3), colors
+
+
+__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "vertex_normals", "to8b", "write_ply", "read_ply")

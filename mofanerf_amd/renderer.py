@@ -601,5 +601,96 @@ class Renderer(torch.nn.Module):
         self.check_launches(block=True)                     # (the copies above already waited for the device)
         return out
 
+    # ------------------------------------------------------------------------------------------------
+    def _set_codes(self, shapeCodes, expType, expCodes):
+        """The conditioning of a geometry query, stored on ``self`` as ``render_fitting`` stores it: the shape code, the expression slot
+        and — when given — the expression code at slot 20 (render_class.py:354-437)."""
+        if shapeCodes is None:
+            raise lib.MofaError("shapeCodes is required")
+        self.shapeCodes = shapeCodes
+        self.expType = int(expType)
+        if expCodes is not None:
+            if len(self.expCodes_Sigma) == 20:
+                self.expCodes_Sigma.append(expCodes)
+            else:
+                self.expCodes_Sigma[20] = expCodes
+
+    def query_density(self, network, pts=None, *, bounds=None, resolution=None, shapeCodes, expType=20, expCodes=None, netchunk=None):
+        """The network's density — the pre-ReLU ``raw[..., 3]`` of ``run_network``, bit for bit — at explicit points ``pts [N,3]``
+        (returns ``[N]``) or on the grid ``bounds = ((x0,y0,z0), (x1,y1,z1))`` x ``resolution = (nx,ny,nz)`` (returns ``[nx,ny,nz]``, sample
+        (i,j,k) at lo + (i,j,k) * step, step = (hi - lo) / (n - 1) in float32).  Density depends on the point, the shape code and the
+        expression code only (models/model.py:121-128), so the texture branch, the view layer and the rgb head are not run
+        (``mofa_net_density``).  Works in chunks of ``netchunk`` points (default ``self.netchunk``); the result does not depend on the
+        chunk size.  Inference only: no autograd graph whatever ``torch.is_grad_enabled()`` says.  Waits for the launch verdicts
+        (``check_launches(block=True)``) before it returns."""
+        from . import mesh
+        if (pts is None) == (bounds is None or resolution is None):
+            raise lib.MofaError("query_density: give pts, or bounds and resolution")
+        chunk = int(netchunk if netchunk is not None else self.netchunk)
+        if chunk < 1:
+            raise lib.MofaError(f"query_density: netchunk = {chunk}")
+        self._set_codes(shapeCodes, expType, expCodes)
+        h = self._hip(network)
+        dev = next(unwrap(network).parameters()).device
+        if dev.type != "cuda":
+            raise lib.MofaError("query_density: the network must live on the GPU (net.cuda()); there is no CPU path")
+        with torch.no_grad():
+            # the texture code feeds only the uv layers, which a density query does not run: zeros fold as well as any code
+            folded = self._fold_codes(network, torch.zeros(h.ch_tex, dtype=torch.float32, device=dev)).clone()
+            if pts is not None:
+                if not torch.is_tensor(pts) or pts.dim() != 2 or pts.shape[-1] != 3:
+                    raise lib.MofaError(f"query_density: pts must be a [N,3] tensor, got {getattr(pts, 'shape', type(pts))}")
+                if not pts.is_cuda:
+                    raise lib.MofaError("query_density: pts is a CPU tensor; there is no CPU path")
+                p = pts.detach().float().contiguous()
+                out = torch.empty(p.shape[0], dtype=torch.float32, device=p.device)
+                for i in range(0, p.shape[0], chunk):
+                    h.density_points(p[i:i + chunk], out[i:i + chunk], folded)
+            else:
+                res, lo, step = mesh.grid_spec(bounds, resolution)
+                n = res[0] * res[1] * res[2]
+                out = torch.empty(n, dtype=torch.float32, device=dev)
+                buf = torch.empty(min(chunk, n), 3, dtype=torch.float32, device=dev)
+                for i in range(0, n, chunk):
+                    m = min(chunk, n - i)
+                    mesh.grid_points(res, lo, step, i, m, buf[:m])
+                    h.density_points(buf[:m], out[i:i + m], folded)
+                out = out.reshape(res)
+        self.check_launches(block=True)
+        return out
+
+    def extract_mesh(self, network, *, bounds, resolution, level, shapeCodes, expType=20, expCodes=None, uvCodes=None, colors=False,
+                     netchunk=None):
+        """Triangle mesh of the face: ``{density >= level}`` over the grid of :meth:`query_density`, by marching tetrahedra on the GPU
+        (``mofa_iso_count`` / ``mofa_iso_emit``).  Returns ``(verts [V,3] float32, faces [F,3] int32)`` — watertight, normals
+        ``(v1 - v0) x (v2 - v0)`` toward lower density — plus, with ``colors=True`` (needs ``uvCodes``), ``colors [V,3]`` in [0,1]:
+        ``sigmoid(raw[..., :3])`` of the full ``run_network`` at each vertex, looking straight at the surface (view direction = minus the
+        area-weighted vertex normal).  ``level`` has no default: no iso-level of a trained MoFaNeRF has been measured.  A density grid
+        with a non-finite value raises ``MofaError``."""
+        from . import mesh
+        if level is None or not np.isfinite(float(level)):
+            raise lib.MofaError(f"extract_mesh: level must be a finite number (got {level})")
+        if colors and uvCodes is None:
+            raise lib.MofaError("extract_mesh: colors=True needs uvCodes (the texture code the colours are evaluated with)")
+        grid = self.query_density(network, bounds=bounds, resolution=resolution, shapeCodes=shapeCodes, expType=expType,
+                                  expCodes=expCodes, netchunk=netchunk)
+        _, lo, step = mesh.grid_spec(bounds, resolution)
+        with torch.no_grad():
+            verts, faces = mesh.iso_surface(grid, float(level), lo, step)
+            if not colors:
+                return verts, faces
+            rgb = torch.empty(0, 3, dtype=torch.float32, device=verts.device)
+            if verts.shape[0]:
+                vd = (-mesh.vertex_normals(verts, faces)).contiguous()
+                self.decoding_texCodes = uvCodes.to(verts.device)
+                keep, self.netchunk = self.netchunk, int(netchunk if netchunk is not None else self.netchunk)
+                try:
+                    raw = self.run_network(verts[:, None, :], vd, network)
+                finally:
+                    self.netchunk = keep
+                rgb = torch.sigmoid(raw[:, 0, :3])
+        self.check_launches(block=True)
+        return verts, faces, rgb
+
 
 myRenderer = Renderer   # the reference's class name
