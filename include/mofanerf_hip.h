@@ -202,6 +202,51 @@ int mofa_iso_count(const float* grid, int64_t nx, int64_t ny, int64_t nz, float 
 int mofa_iso_emit(const float* grid, int64_t nx, int64_t ny, int64_t nz, const float lo[3], const float step[3], float level, void* workspace,
                   float* verts, int32_t* faces, void* stream);
 
+/* Narrow-band ("sparse brick") extraction: the mesh of mofa_iso_count / mofa_iso_emit on the same fine lattice (the grid above with
+ * lo / step), with densities asked for only in bricks the surface passes through.  brick = B in {4, 8, 16}, and (n - 1) % B == 0 on every
+ * axis; brick (bi,bj,bk) covers the cells [bi B, (bi+1) B) per axis (index (bi * by + bj) * bz + bk, b_a = (n_a - 1) / B bricks per axis)
+ * and samples its (B+1)^3 lattice points, local l = (li (B+1) + lj) (B+1) + lk, global i = bi B + li.  Inside, edges, edge_id, vertex
+ * arithmetic and orientation are those of mofa_iso_*; a point evaluated twice must give the same bits (the density is a function of the
+ * point).  The caller drives the rounds and supplies every density:
+ *   seed   the brick-corner lattice, corner c = (ci (by+1) + cj) (bz+1) + ck at lattice point (ci B, cj B, ck B)
+ *          (mofa_band_corner_points); mofa_band_seed activates every brick whose 8 corners are not all on one side of the level;
+ *   round  mofa_band_points gives the (B+1)^3 points of each brick just activated (n_new = counts[0] of the last seed / grow, point
+ *          p = q (B+1)^3 + l of the q-th of them); the caller writes their densities to sigma[(n_active - n_new) (B+1)^3 + p]
+ *          (n_active = counts[1]; sigma keeps every earlier round's densities); mofa_band_grow then activates every neighbour brick
+ *          (across a face, edge or corner) that an outer-layer cell (local index 0 or B-1 on some axis) with a triangle of those bricks
+ *          touches; repeat while counts[0] > 0;
+ *   mesh   mofa_band_count (V, F) and mofa_band_emit, as for mofa_iso_*.
+ * Every connected component of the iso-surface (connected through shared crossing edges) that passes through a seeded brick is
+ * extracted completely and exactly; a component inside bricks whose corners do not straddle the level is missed.  Vertices come by
+ * active brick (ascending index), then by edge_id within the brick (a lattice point belongs to brick min(i / B, b_a - 1) per axis and
+ * owns the edges leaving it); faces by brick, cell (C order within the brick), tet, triangle; edge_ids[v] is the vertex's edge_id, so
+ * ordering the vertices by it gives mofa_iso_emit's numbering.  No atomics: the same bytes on every run and at every chunk size.
+ * Memory: the band workspace is O(1) per brick of the brick grid; the mesh workspace and sigma grow with the active bricks only.
+ * Every count is written to DEVICE memory (int64).  lo / step: HOST arrays (finite, step > 0).  The level must be finite.  The grid
+ * needs 2 <= n < 2^24 per axis and fewer than 2^31 brick corners.  mofa_band_count and mofa_band_emit read the workspace's active count
+ * back (a host synchronisation) and return MOFA_EINVAL unless n_active equals it; mofa_band_emit also reads V and F back and returns
+ * MOFA_EINVAL, writing nothing, when either exceeds 2^31 - 1. */
+size_t mofa_band_workspace_bytes(int64_t nx, int64_t ny, int64_t nz, int32_t brick);   /* 0 for a grid / brick that is refused */
+size_t mofa_band_mesh_bytes(int32_t brick, int64_t n_active);                          /* 0 for n_active < 1 or a bad brick */
+int mofa_band_corner_points(int64_t nx, int64_t ny, int64_t nz, int32_t brick, const float lo[3], const float step[3], int64_t first, int64_t n,
+                            float* pts, void* stream);                       /* pts[n,3]: corners first .. first+n-1 */
+/* corner_sigma[(b_x+1)(b_y+1)(b_z+1)]: counts[0] = seeded bricks (the first round's list), counts[1] = active bricks */
+int mofa_band_seed(int64_t nx, int64_t ny, int64_t nz, int32_t brick, const float* corner_sigma, float level, void* workspace, int64_t* counts,
+                   void* stream);
+int mofa_band_points(int64_t nx, int64_t ny, int64_t nz, int32_t brick, const float lo[3], const float step[3], const void* workspace,
+                     int64_t n_new, int64_t first, int64_t n, float* pts, void* stream);   /* points first .. first+n-1 of the round */
+/* n_new: the host's copy of the last counts[0]; counts[0] = bricks added (the next round's list), counts[1] = active bricks */
+int mofa_band_grow(int64_t nx, int64_t ny, int64_t nz, int32_t brick, const float* sigma, float level, void* workspace, int64_t n_new,
+                   int64_t* counts, void* stream);
+/* after the last round (n_active = the last counts[1] >= 1, mesh_workspace of mofa_band_mesh_bytes(brick, n_active)): counts[0] = V,
+ * counts[1] = F; bricks (DEVICE int64[n_active], may be NULL) = the active brick indices in ascending order */
+int mofa_band_count(int64_t nx, int64_t ny, int64_t nz, int32_t brick, const float* sigma, float level, void* workspace, int64_t n_active,
+                    void* mesh_workspace, int64_t* counts, int64_t* bricks, void* stream);
+/* with the SAME sigma, level and workspaces afterwards: verts [V,3] (float), edge_ids [V] (int64), faces [F,3] (int32 vertex ids) */
+int mofa_band_emit(int64_t nx, int64_t ny, int64_t nz, int32_t brick, const float lo[3], const float step[3], const float* sigma, float level,
+                   const void* workspace, int64_t n_active, const void* mesh_workspace, float* verts, int64_t* edge_ids, int32_t* faces,
+                   void* stream);
+
 /* ---- backward (run_fit.py:305-313 photometric fitting, run_train.py:333-357 training) -----------------------
  * Backward of mofa_net_forward given d_raw [n_rays,S,4] and the tape (fp32, or mask-only when d_weights == NULL) of that forward:
  *   d_folded  [mofa_net_folded_floats]: gradient w.r.t. every folded bias (sum over points of the ReLU-masked

@@ -58,6 +58,14 @@ SIGNATURES = {
     "mofa_iso_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "mofa_iso_count": (C.c_int, [_fp, _i64, _i64, _i64, C.c_float, _fp, _fp, _fp]),
     "mofa_iso_emit": (C.c_int, [_fp, _i64, _i64, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _fp, _fp, _fp, _fp]),
+    "mofa_band_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
+    "mofa_band_mesh_bytes": (_sz, [_i32, _i64]),
+    "mofa_band_corner_points": (C.c_int, [_i64, _i64, _i64, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float), _i64, _i64, _fp, _fp]),
+    "mofa_band_seed": (C.c_int, [_i64, _i64, _i64, _i32, _fp, C.c_float, _fp, _fp, _fp]),
+    "mofa_band_points": (C.c_int, [_i64, _i64, _i64, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float), _fp, _i64, _i64, _i64, _fp, _fp]),
+    "mofa_band_grow": (C.c_int, [_i64, _i64, _i64, _i32, _fp, C.c_float, _fp, _i64, _fp, _fp]),
+    "mofa_band_count": (C.c_int, [_i64, _i64, _i64, _i32, _fp, C.c_float, _fp, _i64, _fp, _fp, _fp, _fp]),
+    "mofa_band_emit": (C.c_int, [_i64, _i64, _i64, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float), _fp, C.c_float, _fp, _i64, _fp, _fp, _fp, _fp, _fp]),
     "mofa_net_packed_t_floats": (_sz, [NetShape]),
     "mofa_net_tape_floats": (_sz, [NetShape, _i64]),
     "mofa_net_mask_tape_words": (_sz, [NetShape, _i64]),

@@ -1,5 +1,6 @@
 """Geometry export: the grid of a density query, the iso-surface of a density grid on the GPU (``mofa_iso_count`` / ``mofa_iso_emit``,
-marching tetrahedra on the Freudenthal split) and a binary PLY writer / reader.
+marching tetrahedra on the Freudenthal split), the same mesh from a narrow band of bricks around the surface (``band_surface``,
+``mofa_band_*``) and a binary PLY writer / reader.
 
 ``Renderer.query_density`` and ``Renderer.extract_mesh`` are the user-facing entry points; this module holds the pieces they share.
 The mesh is watertight and consistently oriented (normals toward lower density); vertices and faces come out in a fixed order with
@@ -8,6 +9,7 @@ no atomics, so the same grid gives the same bytes every time.  CPU tensors raise
 from __future__ import annotations
 
 import ctypes as C
+import time
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -73,6 +75,127 @@ def iso_surface(grid: torch.Tensor, level: float, lo, step) -> Tuple[torch.Tenso
         lib.check(L.mofa_iso_emit(lib.ptr(g), nx, ny, nz, _f3(lo), _f3(step), level, ws.data_ptr(), lib.ptr(verts), faces.data_ptr(),
                                   lib.stream()), "mofa_iso_emit")
     return verts, faces
+
+
+BRICKS = (4, 8, 16)
+
+
+def band_surface(density_fn, resolution, lo, step, level, brick, chunk, verify=None, timing=False):
+    """Narrow-band ("sparse brick") extraction of ``{density >= level}`` on the fine lattice of :func:`grid_points` (``mofa_band_*``):
+    densities are asked for only at the brick-corner lattice and in the ``brick^3``-cell bricks the surface passes through, so the work
+    follows the surface, not the volume.  ``density_fn(pts [n,3] float32 GPU) -> [n]`` is any GPU float32 function of the point (a point
+    asked for twice must give the same bits); it is called with at most ``chunk`` points.  ``verify()``, if given, runs after each
+    round's densities and before any kernel reads them (``Renderer.extract_mesh`` waits for its launch verdicts there).
+
+    A brick is seeded when its 8 corners are not all on one side of the level; an outer-layer cell of a newly evaluated brick that holds a
+    triangle activates every neighbour brick it touches, until nothing is added.  Every connected component of the surface that passes
+    through a seeded brick comes out exactly as :func:`iso_surface` would give it on the dense grid; a component that lies inside
+    bricks without a corner sign change is missed.
+
+    Returns ``(verts [V,3] float32, faces [F,3] int32, edge_ids [V] int64, stats)``: vertices by brick, then edge id; faces by brick,
+    cell, tet, triangle; ordering the vertices by ``edge_ids`` gives :func:`iso_surface`'s numbering.  ``stats``: ``bricks_total``,
+    ``bricks_seeded``, ``bricks_active``, ``rounds`` (growth passes that added bricks), ``points_evaluated`` (corners + active bricks'
+    points, apron included), ``points_dense`` (nx ny nz), ``active_bricks`` (int64 numpy, ascending) and, with ``timing=True``,
+    ``times`` (seconds of the seed, band density, growth and meshing phases; each phase ends with a device synchronisation).  A
+    non-finite density raises ``MofaError``."""
+    nx, ny, nz = (int(v) for v in resolution)
+    B = int(brick)
+    level = float(level)
+    if B not in BRICKS:
+        raise lib.MofaError(f"band_surface: brick = {brick} (want one of {BRICKS})")
+    if not np.isfinite(level):
+        raise lib.MofaError(f"band_surface: the level must be finite (got {level})")
+    chunk = int(chunk)
+    if chunk < 1:
+        raise lib.MofaError(f"band_surface: chunk = {chunk}")
+    L = lib.load()
+    nbytes = L.mofa_band_workspace_bytes(nx, ny, nz, B)
+    if nbytes == 0:
+        raise lib.MofaError(f"band_surface: grid {nx} x {ny} x {nz} with bricks of {B} is refused ((n - 1) % B == 0 and 2 <= n < 2^24 "
+                            f"per axis, fewer than 2^31 brick corners)")
+    lo3, st3 = _f3(lo), _f3(step)
+    if not all(np.isfinite(v) for v in (*lo3, *st3)) or min(st3) <= 0:
+        raise lib.MofaError(f"band_surface: lo = {list(lo3)}, step = {list(st3)} (want finite, step > 0)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = lib.stream()
+    bx, by, bz = (nx - 1) // B, (ny - 1) // B, (nz - 1) // B
+    P = (B + 1) ** 3
+    times = {"seed": 0.0, "density": 0.0, "growth": 0.0, "mesh": 0.0}
+    clock = [time.perf_counter()]
+
+    def lap(phase):
+        if timing:
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            times[phase] += now - clock[0]
+            clock[0] = now
+
+    def evaluate(fill, n, out, what):
+        buf = torch.empty(min(chunk, n), 3, dtype=torch.float32, device=dev)
+        for i in range(0, n, chunk):
+            m = min(chunk, n - i)
+            fill(i, m, buf[:m])
+            d = density_fn(buf[:m])
+            if not torch.is_tensor(d) or d.shape != (m,) or d.dtype != torch.float32 or d.device != dev:
+                raise lib.MofaError(f"band_surface: density_fn must return [{m}] float32 on {dev}, got "
+                                    f"{getattr(d, 'shape', type(d))} {getattr(d, 'dtype', '')} {getattr(d, 'device', '')}")
+            out[i:i + m] = d
+        if verify is not None:
+            verify()
+        if not bool(torch.isfinite(out[:n]).all()):
+            raise lib.MofaError(f"band_surface: density_fn returned non-finite values at the {what}")
+
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    # seed: the brick-corner lattice
+    n_corners = (bx + 1) * (by + 1) * (bz + 1)
+    corner_sigma = torch.empty(n_corners, dtype=torch.float32, device=dev)
+    evaluate(lambda i, m, buf: lib.check(L.mofa_band_corner_points(nx, ny, nz, B, lo3, st3, i, m, lib.ptr(buf), stream),
+                                         "mofa_band_corner_points"), n_corners, corner_sigma, "brick corners")
+    lib.check(L.mofa_band_seed(nx, ny, nz, B, lib.ptr(corner_sigma), level, ws.data_ptr(), counts.data_ptr(), stream), "mofa_band_seed")
+    n_new, n_active = (int(v) for v in counts.cpu())
+    seeded, rounds = n_new, 0
+    del corner_sigma
+    lap("seed")
+    # rounds: evaluate the bricks just activated, grow from them
+    sigma = torch.empty(max(n_active, 1) * P, dtype=torch.float32, device=dev)
+    while n_new:
+        base = n_active - n_new
+        if sigma.numel() < n_active * P:                      # (slots of every earlier round stay where they are)
+            grown = torch.empty(max(n_active, 2 * sigma.numel() // P) * P, dtype=torch.float32, device=dev)
+            grown[:base * P] = sigma[:base * P]
+            sigma = grown
+        evaluate(lambda i, m, buf: lib.check(L.mofa_band_points(nx, ny, nz, B, lo3, st3, ws.data_ptr(), n_new, i, m, lib.ptr(buf), stream),
+                                             "mofa_band_points"), n_new * P, sigma[base * P:n_active * P], "band points")
+        lap("density")
+        lib.check(L.mofa_band_grow(nx, ny, nz, B, lib.ptr(sigma), level, ws.data_ptr(), n_new, counts.data_ptr(), stream), "mofa_band_grow")
+        n_new, n_active = (int(v) for v in counts.cpu())
+        rounds += n_new > 0
+        lap("growth")
+    stats = {"bricks_total": bx * by * bz, "bricks_seeded": seeded, "bricks_active": n_active, "rounds": rounds,
+             "points_evaluated": n_corners + n_active * P, "points_dense": nx * ny * nz}
+    verts = torch.empty(0, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(0, 3, dtype=torch.int32, device=dev)
+    edge_ids = torch.empty(0, dtype=torch.int64, device=dev)
+    bricks = torch.empty(n_active, dtype=torch.int64, device=dev)
+    if n_active:
+        mws = torch.empty(L.mofa_band_mesh_bytes(B, n_active), dtype=torch.uint8, device=dev)
+        lib.check(L.mofa_band_count(nx, ny, nz, B, lib.ptr(sigma), level, ws.data_ptr(), n_active, mws.data_ptr(), counts.data_ptr(),
+                                    bricks.data_ptr(), stream), "mofa_band_count")
+        V, F = (int(v) for v in counts.cpu())
+        if V > 2 ** 31 - 1 or F > 2 ** 31 - 1:
+            raise lib.MofaError(f"band_surface: {V} vertices / {F} faces exceed the int32 face indices (2^31 - 1)")
+        verts = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+        edge_ids = torch.empty(V, dtype=torch.int64, device=dev)
+        if V and F:
+            lib.check(L.mofa_band_emit(nx, ny, nz, B, lo3, st3, lib.ptr(sigma), level, ws.data_ptr(), n_active, mws.data_ptr(),
+                                       lib.ptr(verts), edge_ids.data_ptr(), faces.data_ptr(), stream), "mofa_band_emit")
+    stats["active_bricks"] = bricks.cpu().numpy()
+    lap("mesh")
+    if timing:
+        stats["times"] = times
+    return verts, faces, edge_ids, stats
 
 
 def vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
@@ -155,4 +278,4 @@ def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
     return verts, np.ascontiguousarray(frec["i"]).astype(np.int32).reshape(-1, 3), colors
 
 
-__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "vertex_normals", "to8b", "write_ply", "read_ply")
+__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "vertex_normals", "to8b", "write_ply", "read_ply")

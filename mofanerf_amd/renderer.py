@@ -105,6 +105,7 @@ class Renderer(torch.nn.Module):
         self.n_streams = int(os.environ.get("MOFA_STREAMS", "1"))   # concurrent sub-batches of the inference path (render_rays)
         self._streams = {}
         self.png_sink = None      # optional mofanerf_amd.io.PngSink shared by consecutive render_path calls (bulk renders)
+        self.mesh_stats = None    # the statistics of the last narrow-band extract_mesh (mesh.band_surface's, plus "edge_ids")
 
     @staticmethod
     def _freqs(fn, default, what):
@@ -660,23 +661,34 @@ class Renderer(torch.nn.Module):
         return out
 
     def extract_mesh(self, network, *, bounds, resolution, level, shapeCodes, expType=20, expCodes=None, uvCodes=None, colors=False,
-                     netchunk=None):
+                     netchunk=None, brick=None):
         """Triangle mesh of the face: ``{density >= level}`` over the grid of :meth:`query_density`, by marching tetrahedra on the GPU
         (``mofa_iso_count`` / ``mofa_iso_emit``).  Returns ``(verts [V,3] float32, faces [F,3] int32)`` — watertight, normals
         ``(v1 - v0) x (v2 - v0)`` toward lower density — plus, with ``colors=True`` (needs ``uvCodes``), ``colors [V,3]`` in [0,1]:
         ``sigmoid(raw[..., :3])`` of the full ``run_network`` at each vertex, looking straight at the surface (view direction = minus the
         area-weighted vertex normal).  ``level`` has no default: no iso-level of a trained MoFaNeRF has been measured.  A density grid
-        with a non-finite value raises ``MofaError``."""
+        with a non-finite value raises ``MofaError``.
+
+        ``brick = B`` (4, 8 or 16; ``(n - 1) % B == 0`` on every axis) takes the narrow-band path (``mesh.band_surface``): the density is
+        evaluated only at the brick corners and in the bricks the surface passes through, in chunks of ``netchunk`` points, with the
+        folded codes of :meth:`query_density`.  Every surface component that passes through a brick whose corners straddle the level
+        comes out exactly as on the dense grid, its vertices numbered by brick (``self.mesh_stats["edge_ids"]`` gives each vertex's edge
+        id; ordering by it gives the dense numbering); smaller components are missed.  ``self.mesh_stats`` keeps the statistics of the
+        last band extraction."""
         from . import mesh
         if level is None or not np.isfinite(float(level)):
             raise lib.MofaError(f"extract_mesh: level must be a finite number (got {level})")
         if colors and uvCodes is None:
             raise lib.MofaError("extract_mesh: colors=True needs uvCodes (the texture code the colours are evaluated with)")
-        grid = self.query_density(network, bounds=bounds, resolution=resolution, shapeCodes=shapeCodes, expType=expType,
-                                  expCodes=expCodes, netchunk=netchunk)
-        _, lo, step = mesh.grid_spec(bounds, resolution)
+        res, lo, step = mesh.grid_spec(bounds, resolution)
+        if brick is None:
+            grid = self.query_density(network, bounds=bounds, resolution=resolution, shapeCodes=shapeCodes, expType=expType,
+                                      expCodes=expCodes, netchunk=netchunk)
         with torch.no_grad():
-            verts, faces = mesh.iso_surface(grid, float(level), lo, step)
+            if brick is None:
+                verts, faces = mesh.iso_surface(grid, float(level), lo, step)
+            else:
+                verts, faces = self._band_mesh(network, res, lo, step, float(level), int(brick), shapeCodes, expType, expCodes, netchunk)
             if not colors:
                 return verts, faces
             rgb = torch.empty(0, 3, dtype=torch.float32, device=verts.device)
@@ -691,6 +703,30 @@ class Renderer(torch.nn.Module):
                 rgb = torch.sigmoid(raw[:, 0, :3])
         self.check_launches(block=True)
         return verts, faces, rgb
+
+    def _band_mesh(self, network, res, lo, step, level, brick, shapeCodes, expType, expCodes, netchunk):
+        """extract_mesh's narrow-band path: mesh.band_surface over HipNet.density_points; the statistics go to self.mesh_stats."""
+        from . import mesh
+        chunk = int(netchunk if netchunk is not None else self.netchunk)
+        if chunk < 1:
+            raise lib.MofaError(f"extract_mesh: netchunk = {chunk}")
+        self._set_codes(shapeCodes, expType, expCodes)
+        h = self._hip(network)
+        dev = next(unwrap(network).parameters()).device
+        if dev.type != "cuda":
+            raise lib.MofaError("extract_mesh: the network must live on the GPU (net.cuda()); there is no CPU path")
+        folded = self._fold_codes(network, torch.zeros(h.ch_tex, dtype=torch.float32, device=dev)).clone()
+
+        def density(pts):
+            out = torch.empty(pts.shape[0], dtype=torch.float32, device=pts.device)
+            h.density_points(pts, out, folded)
+            return out
+
+        verts, faces, edge_ids, stats = mesh.band_surface(density, res, lo, step, level, brick, chunk,
+                                                          verify=lambda: self.check_launches(block=True))
+        stats["edge_ids"] = edge_ids
+        self.mesh_stats = stats
+        return verts, faces
 
 
 myRenderer = Renderer   # the reference's class name

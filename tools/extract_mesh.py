@@ -8,8 +8,16 @@ saving_uv, saving_exp) or from ``synth.codes``.  ``--bounds`` and ``--level`` ar
 been measured, so there are no defaults.
 
   python tools/extract_mesh.py --synthetic 10 1024 --bounds -1 -1 -1 1 1 1 --resolution 256 256 256 --level 0 --out face.ply --time
+
+``--brick B`` takes the narrow-band path (densities only in the bricks of B^3 cells the surface passes through; (n - 1) % B == 0 on
+every axis), which reaches grids the dense path refuses; ``--compare-dense`` also runs the dense path and exits non-zero unless the two
+meshes are equal after renumbering by edge id:
+
+  python tools/extract_mesh.py --synthetic 10 1024 --bounds -1 -1 -1 1 1 1 --resolution 513 513 513 --level 0 --brick 8 \
+      --compare-dense --time
 """
 import argparse
+import itertools
 import os
 import sys
 import time
@@ -59,17 +67,24 @@ def main(argv=None):
     ap.add_argument("--colors", action="store_true", help="per-vertex colours from the full network (needs the texture code)")
     ap.add_argument("--netchunk", type=int, default=None, help="points per density launch (default: the renderer's netchunk)")
     ap.add_argument("--out", default="mesh.ply")
-    ap.add_argument("--time", action="store_true", help="after a warm-up: density and extraction times, density vs forward_points")
+    ap.add_argument("--time", action="store_true", help="after a warm-up: density and extraction times, density vs forward_points "
+                    "(with --brick: the band's seed / density / growth / meshing split against the dense path)")
+    ap.add_argument("--brick", type=int, default=None, help="narrow-band extraction with bricks of B^3 cells (4, 8 or 16)")
+    ap.add_argument("--compare-dense", action="store_true", help="with --brick: also run the dense path and require equal meshes")
     a = ap.parse_args(argv)
+    if a.compare_dense and a.brick is None:
+        ap.error("--compare-dense needs --brick")
     dev = torch.device("cuda", torch.cuda.current_device())
     render, net, bm, uv, exp = load(a, dev)
     bounds = (tuple(a.bounds[:3]), tuple(a.bounds[3:]))
     res = tuple(a.resolution)
     kw = dict(bounds=bounds, resolution=res, shapeCodes=bm, expType=20, expCodes=exp, netchunk=a.netchunk)
-    out = render.extract_mesh(net, level=a.level, uvCodes=uv if a.colors else None, colors=a.colors, **kw)
+    out = render.extract_mesh(net, level=a.level, uvCodes=uv if a.colors else None, colors=a.colors, brick=a.brick, **kw)
     verts, faces = out[0], out[1]
     mesh.write_ply(a.out, verts, faces, out[2] if a.colors else None)
     print(f"wrote {a.out}: V = {verts.shape[0]}, F = {faces.shape[0]}")
+    if a.brick is not None:
+        return band_report(a, render, net, kw, verts, faces)
     if not a.time:
         return
 
@@ -109,6 +124,112 @@ def main(argv=None):
     print(f"density speed-up over the full forward: {t_full / t_density:.3f}x  (bit-identical sigma)")
     print(f"extraction (count + read + emit): {t_iso * 1e3:9.3f} ms  = {100 * t_iso / t_density:.3f} % of the density query")
     print(f"V = {v2.shape[0]}, F = {f2.shape[0]}")
+
+
+def renumbered(verts, faces, edge_ids):
+    """The band mesh in the dense numbering (vertices by edge id) with its faces as a canonical multiset (each triangle rotated to start
+    at its smallest index, orientation kept; rows sorted), on the GPU."""
+    order = torch.argsort(edge_ids)
+    new_of_old = torch.empty_like(order)
+    new_of_old[order] = torch.arange(order.numel(), device=order.device)
+    return verts[order], canonical(new_of_old[faces.long()])
+
+
+def canonical(faces):
+    f = faces.long()
+    if f.shape[0] == 0:
+        return f
+    r = torch.argmin(f, dim=1, keepdim=True)
+    f = torch.gather(f, 1, (r + torch.arange(3, device=f.device)) % 3)
+    for c in (2, 1, 0):                                   # lexicographic: stable sorts from the last column to the first
+        f = f[torch.sort(f[:, c], stable=True).indices]
+    return f
+
+
+def bricks_with_surface(grid, level, B):
+    """[bx,by,bz] bool: the brick holds a cell whose 8 corners are not all on one side of the level (a cell with a triangle)."""
+    inside = grid >= level
+    nx, ny, nz = grid.shape
+    n = torch.zeros(nx - 1, ny - 1, nz - 1, dtype=torch.uint8, device=grid.device)
+    for dx, dy, dz in itertools.product((0, 1), repeat=3):
+        n += inside[dx:nx - 1 + dx, dy:ny - 1 + dy, dz:nz - 1 + dz]
+    mixed = (n > 0) & (n < 8)
+    bx, by, bz = (nx - 1) // B, (ny - 1) // B, (nz - 1) // B
+    return mixed.reshape(bx, B, by, B, bz, B).any(dim=5).any(dim=3).any(dim=1)
+
+
+def band_report(a, render, net, kw, verts, faces):
+    """--brick: the band's statistics, with --time its time split against the dense path, with --compare-dense the equality check."""
+    st = render.mesh_stats
+    frac = st["bricks_active"] / max(st["bricks_total"], 1)
+    print(f"bricks of {a.brick}^3 cells: {st['bricks_active']} of {st['bricks_total']} active ({100 * frac:.2f} %), "
+          f"{st['bricks_seeded']} seeded, {st['rounds']} growth rounds")
+    print(f"points evaluated: {st['points_evaluated']} of {st['points_dense']} dense "
+          f"({100 * st['points_evaluated'] / st['points_dense']:.2f} %)")
+    res = kw["resolution"]
+    dense_ok = mesh.lib.load().mofa_iso_workspace_bytes(*res) != 0
+    t_dense = None
+    if a.time:
+        # the band again (warm), phase by phase: each phase ends with a device synchronisation
+        _, lo, step = mesh.grid_spec(kw["bounds"], res)
+        render._set_codes(kw["shapeCodes"], kw["expType"], kw["expCodes"])
+        h = render._hip(net)
+        chunk = int(a.netchunk or render.netchunk)
+        with torch.no_grad():
+            folded = render._fold_codes(net, torch.zeros(h.ch_tex, device=verts.device)).clone()
+
+            def density(pts):
+                o = torch.empty(pts.shape[0], dtype=torch.float32, device=pts.device)
+                h.density_points(pts, o, folded)
+                return o
+
+            t0 = time.perf_counter()
+            _, _, _, ts = mesh.band_surface(density, res, lo, step, a.level, a.brick, chunk, verify=lambda: render.check_launches(block=True),
+                                         timing=True)
+            t_band = time.perf_counter() - t0
+        tm = ts["times"]
+        other = tm["seed"] + tm["growth"] + tm["mesh"]
+        print(f"band total {t_band * 1e3:9.2f} ms:  seed (corner density + flags) {tm['seed'] * 1e3:.2f} ms, band density "
+              f"{tm['density'] * 1e3:.2f} ms, growth {tm['growth'] * 1e3:.2f} ms, meshing {tm['mesh'] * 1e3:.2f} ms")
+        n_corner = ts["points_evaluated"] - ts["bricks_active"] * (a.brick + 1) ** 3
+        print(f"  corner points {n_corner}, band points {ts['points_evaluated'] - n_corner}; "
+              f"seed + growth + meshing = {100 * other / max(tm['density'], 1e-12):.2f} % of the band density time")
+        if not dense_ok:
+            print(f"dense path: grid {res[0]}x{res[1]}x{res[2]} is refused (7 nx ny nz >= 2^31)")
+    if a.compare_dense and not dense_ok:
+        raise SystemExit(f"--compare-dense: the dense path refuses grid {res[0]}x{res[1]}x{res[2]}")
+    if not (a.compare_dense or (a.time and dense_ok)):
+        return
+    # the dense path (query_density + iso_surface, which is what extract_mesh runs), timed once
+    _, lo, step = mesh.grid_spec(kw["bounds"], res)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    grid = render.query_density(net, **kw)
+    with torch.no_grad():
+        dv, df = mesh.iso_surface(grid, a.level, lo, step)
+    torch.cuda.synchronize()
+    t_dense = time.perf_counter() - t0
+    bv, bf = renumbered(verts, faces, st["edge_ids"])
+    same = bv.shape == dv.shape and torch.equal(bv.view(torch.int32), dv.view(torch.int32)) and torch.equal(bf, canonical(df))
+    print(f"dense: V = {dv.shape[0]}, F = {df.shape[0]} (band: V = {verts.shape[0]}, F = {faces.shape[0]});  band == dense after "
+          f"renumbering: {same}")
+    if a.time:
+        print(f"dense query_density + iso_surface {t_dense * 1e3:9.2f} ms;  band speed-up {t_dense / t_band:.2f}x"
+              + ("" if same else "  (NOT like for like: the band mesh is a subset of the dense mesh)"))
+    if not same:
+        # what a band holding the whole dense surface would have cost: every brick with a surface cell, plus the bricks growth added
+        need = bricks_with_surface(grid, a.level, a.brick).reshape(-1)
+        need[torch.as_tensor(st["active_bricks"], device=need.device)] = True
+        n_need = int(need.sum())
+        pts = st["points_evaluated"] + (n_need - st["bricks_active"]) * (a.brick + 1) ** 3
+        print(f"bricks holding the dense surface or active: {n_need} ({100 * n_need / st['bricks_total']:.2f} %), the band found "
+              f"{st['bricks_active']}; a band over all of them evaluates {pts} points ({100 * pts / st['points_dense']:.2f} % of dense)")
+        if a.time:
+            t_full = tm["seed"] + tm["growth"] + tm["mesh"] + tm["density"] * (pts - n_corner) / max(st["points_evaluated"] - n_corner, 1)
+            print(f"  at the measured band density rate that is about {t_full * 1e3:.0f} ms: a like-for-like speed-up of about "
+                  f"{t_dense / t_full:.2f}x (estimate)")
+    if a.compare_dense and not same:
+        raise SystemExit("the band mesh differs from the dense mesh (a surface component without a seeded brick)")
 
 
 if __name__ == "__main__":
