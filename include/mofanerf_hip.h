@@ -247,6 +247,40 @@ int mofa_band_emit(int64_t nx, int64_t ny, int64_t nz, int32_t brick, const floa
                    const void* workspace, int64_t n_active, const void* mesh_workspace, float* verts, int64_t* edge_ids, int32_t* faces,
                    void* stream);
 
+/* ---- occupancy-culled rendering: skip the network where an occupancy grid says the space is empty ---------------------------------
+ * The grid lives on the lattice of mofa_grid_points (nx x ny x nz samples at lo + (i,j,k) step): (nx-1)(ny-1)(nz-1) cells, one byte
+ * each (0 / 1), cell index (i (ny-1) + j) (nz-1) + k.  The lattice needs 2 <= n < 2^24 per axis and fewer than 2^31 cells.
+ *   mofa_occ_cells   cells[c] = 1 iff one of the cell's 8 corner samples of grid [nx,ny,nz] is > threshold (NaN is not); merge != 0 ORs
+ *                    into what cells already holds (the union over several networks).  The threshold must be finite.
+ *   mofa_occ_dilate  out[c] = 1 iff a cell within Chebyshev distance `dilate` (0 .. 8, clipped at the borders) of c is set in cells:
+ *                    a separable maximum, three passes through `scratch`; cells, scratch and out are three different buffers of one
+ *                    byte per cell.
+ * A pass of n_rays x S samples (fewer than 2^31), sample e = r S + s at p = o_r + d_r z_{r,s} with the multiply and the add rounded
+ * separately (the point mofa_net_forward forms); z [n_rays,S] (z_row_stride = S) or one shared row (stride 0).  Per axis, in fp32:
+ * t = (p - lo) / step (correctly rounded), inside = t >= 0 && t <= (float)(n - 1) (NaN: outside), c = min((int)t, n - 2).  A sample is
+ * KEPT iff it is inside on all three axes and its cell is set.
+ *   mofa_occ_classify  flags[e] = kept (one byte per sample); the 64-bit exclusive scan of the flags goes to `workspace`
+ *                      (mofa_occ_workspace_bytes(n_rays S) bytes) and counts[0] = n_kept (int64, DEVICE).  lo / step: HOST arrays
+ *                      (finite, step > 0).
+ *   mofa_occ_gather    with the same pass, flags and workspace afterwards, n_kept = the host's copy of counts[0] (>= 1): the kept samples
+ *                      in ascending e — pts [n_kept,3] (their points), dirs [n_kept,3] (their rays' view directions), index [n_kept]
+ *                      (int32: e).  What mofa_net_forward takes as explicit points with S = 1.
+ *   mofa_occ_scatter   raw [n_samples,4] = raw_kept [n_kept,4] row scan[e] for a kept sample, (0,0,0,0) for a skipped one: every
+ *                      element is written by this one kernel.  raw_kept may be NULL when n_kept = 0.  Both 16-byte aligned.
+ * No atomics: the same input gives the same bytes.  A slot at or beyond n_kept (a count that does not belong to the flags) is never
+ * written by gather and gives NaN in scatter. */
+size_t mofa_occ_workspace_bytes(int64_t n_samples);   /* 0 for n_samples < 1 or >= 2^31 */
+int mofa_occ_cells(const float* grid, int64_t nx, int64_t ny, int64_t nz, float threshold, int32_t merge, uint8_t* cells, void* stream);
+int mofa_occ_dilate(const uint8_t* cells, int64_t nx, int64_t ny, int64_t nz, int32_t dilate, uint8_t* scratch, uint8_t* out, void* stream);
+int mofa_occ_classify(const float* rays_o, const float* rays_d, const float* z, int64_t z_row_stride, int64_t n_rays, int32_t S,
+                      const uint8_t* cells, int64_t nx, int64_t ny, int64_t nz, const float lo[3], const float step[3], uint8_t* flags,
+                      void* workspace, int64_t* counts, void* stream);
+int mofa_occ_gather(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z, int64_t z_row_stride, int64_t n_rays,
+                    int32_t S, const uint8_t* flags, const void* workspace, int64_t n_kept, float* pts, float* dirs, int32_t* index,
+                    void* stream);
+int mofa_occ_scatter(const float* raw_kept, const uint8_t* flags, const void* workspace, int64_t n_samples, int64_t n_kept, float* raw,
+                     void* stream);
+
 /* ---- backward (run_fit.py:305-313 photometric fitting, run_train.py:333-357 training) -----------------------
  * Backward of mofa_net_forward given d_raw [n_rays,S,4] and the tape (fp32, or mask-only when d_weights == NULL) of that forward:
  *   d_folded  [mofa_net_folded_floats]: gradient w.r.t. every folded bias (sum over points of the ReLU-masked

@@ -301,6 +301,13 @@ using namespace mofa;
 
 extern "C" {
 
+// the scan, for the occupancy kernels' compaction (mofa_occ.hip): out[0..n) = exclusive prefix sums of the bytes in[0..n), aux of
+// mofa_internal_scan_aux(n) elements
+long long mofa_internal_scan_aux(long long n) { return scan_aux(n); }
+int mofa_internal_scan_bytes(const unsigned char* in, long long n, long long* out, long long* aux, void* stream) {
+    return scan_exclusive<unsigned char>(in, n, out, aux, (hipStream_t)stream);
+}
+
 int mofa_grid_points(int64_t nx, int64_t ny, int64_t nz, const float lo[3], const float step[3], int64_t first, int64_t n, float* pts,
                      void* stream) {
     MOFA_REQUIRE(lo && step && pts, "grid_points: null pointer");

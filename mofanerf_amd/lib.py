@@ -66,6 +66,13 @@ SIGNATURES = {
     "mofa_band_grow": (C.c_int, [_i64, _i64, _i64, _i32, _fp, C.c_float, _fp, _i64, _fp, _fp]),
     "mofa_band_count": (C.c_int, [_i64, _i64, _i64, _i32, _fp, C.c_float, _fp, _i64, _fp, _fp, _fp, _fp]),
     "mofa_band_emit": (C.c_int, [_i64, _i64, _i64, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float), _fp, C.c_float, _fp, _i64, _fp, _fp, _fp, _fp, _fp]),
+    "mofa_occ_workspace_bytes": (_sz, [_i64]),
+    "mofa_occ_cells": (C.c_int, [_fp, _i64, _i64, _i64, C.c_float, _i32, _fp, _fp]),
+    "mofa_occ_dilate": (C.c_int, [_fp, _i64, _i64, _i64, _i32, _fp, _fp, _fp]),
+    "mofa_occ_classify": (C.c_int, [_fp, _fp, _fp, _i64, _i64, _i32, _fp, _i64, _i64, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), _fp,
+                                    _fp, _fp, _fp]),
+    "mofa_occ_gather": (C.c_int, [_fp, _fp, _fp, _fp, _i64, _i64, _i32, _fp, _fp, _i64, _fp, _fp, _fp, _fp]),
+    "mofa_occ_scatter": (C.c_int, [_fp, _fp, _fp, _i64, _i64, _fp, _fp]),
     "mofa_net_packed_t_floats": (_sz, [NetShape]),
     "mofa_net_tape_floats": (_sz, [NetShape, _i64]),
     "mofa_net_mask_tape_words": (_sz, [NetShape, _i64]),

@@ -106,6 +106,7 @@ class Renderer(torch.nn.Module):
         self._streams = {}
         self.png_sink = None      # optional mofanerf_amd.io.PngSink shared by consecutive render_path calls (bulk renders)
         self.mesh_stats = None    # the statistics of the last narrow-band extract_mesh (mesh.band_surface's, plus "edge_ids")
+        self.occupancy_stats = None   # the last render* call with an occupancy grid: {"coarse" / "fine": {"samples", "kept"}}, summed over chunks
 
     @staticmethod
     def _freqs(fn, default, what):
@@ -316,8 +317,19 @@ class Renderer(torch.nn.Module):
     # ------------------------------------------------------------------------------------------------
     def render_rays(self, ray_batch, network_fn, N_samples, retraw=False, lindisp=False, perturb=0., N_importance=0,
                     network_fine=None, white_bkgd=False, raw_noise_std=0., network_query_fn=None, verbose=False,
-                    pytest=False):
-        """Coarse + fine volumetric rendering of rays ``self.rays[b0:b1]`` (render_class.py:239-352)."""
+                    pytest=False, occupancy=None):
+        """Coarse + fine volumetric rendering of rays ``self.rays[b0:b1]`` (render_class.py:239-352).
+
+        ``occupancy`` (an ``occupancy.OccupancyGrid``, from :meth:`build_occupancy` or ``occupancy_from_grid``): occupancy-culled
+        rendering — in each pass the network runs only on the samples whose point lies in an occupied cell of the grid (explicit
+        points through ``mofa_net_forward``, in sub-batches of ``netchunk`` points); every other sample gets ``raw = (0,0,0,0)``, hence
+        ``alpha = 0`` and weight 0 exactly.  The frame equals, bit for bit, the un-culled pipeline with those samples' raw values
+        replaced by zero; compositing and the importance resampling are unchanged.  Everything outside the grid's bounds is empty.  The
+        grid lives in the space of the points the network is given: with ``ndc=True`` those are NDC points, so the grid's bounds must be
+        NDC bounds (no conversion is done); the face scripts render with ``ndc=False``.  Inference only (a tensor that asks for a
+        gradient under ``torch.is_grad_enabled()`` is refused) and ``raw_noise_std`` must be 0.  Each pass reads its kept count back to the
+        host (one synchronisation per pass and chunk of rays); ``self.occupancy_stats`` sums samples and kept samples per pass.
+        ``None`` (default): nothing changes."""
         L = self._lib()
         rays = self.rays[ray_batch[0]:ray_batch[1]]
         R, dev = int(rays.shape[0]), rays.device
@@ -418,11 +430,35 @@ class Renderer(torch.nn.Module):
             h.snapshot_verdict()       # ONE snapshot, on the main stream, behind every side stream's launches
             return raw
 
+        def network_culled(net, folded, zv, zs, n_s, which):
+            # classify, compact (one host read: n_kept), network on the kept samples as explicit points with one view direction each
+            # (S = 1), scatter: every element of raw is written by the scatter kernel
+            from .occupancy import CulledPass
+            h = self._hip(net)
+            cp = CulledPass(occupancy, rays_o, rays_d, zv, zs, n_s)
+            stats = self.occupancy_stats.setdefault(which, {"samples": 0, "kept": 0})
+            stats["samples"] += cp.n_samples
+            stats["kept"] += cp.n_kept
+            raw = torch.empty(R, n_s, 4, dtype=torch.float32, device=dev)
+            raw_kept = None
+            if cp.n_kept:
+                pts, dirs, _ = cp.gather(vd)
+                raw_kept = torch.empty(cp.n_kept, 1, 4, dtype=torch.float32, device=dev)
+                per = max(1, int(self.netchunk))
+                for i in range(0, cp.n_kept, per):
+                    h.forward_points(pts[i:i + per], dirs[i:i + per], 1, raw_kept[i:i + per], folded)
+            return cp.scatter(raw_kept, raw)
+
+        if occupancy is not None:
+            self._check_occupancy(occupancy, rays, raw_noise_std, network_fn, network_fine)
+            if self.occupancy_stats is None:
+                self.occupancy_stats = {}
         if getattr(self, "_rays_ref", None) is not self.rays and not getattr(self, "_folds_hoisted", False):
             # called directly on a caller-built self.rays (the reference documents batchify_rays / render_rays as callable once
             # self.rays, shapeCodes, expType and decoding_texCodes are set): fold the per-call codes here (batchify_rays hoists it)
             self._fold_direct(network_fn, network_fine)
-        raw = network(network_fn, self._folded_coarse, z, z_stride, S)
+        raw = (network(network_fn, self._folded_coarse, z, z_stride, S) if occupancy is None else
+               network_culled(network_fn, self._folded_coarse, z, z_stride, S, "coarse"))
         c = composite(raw, z, z_stride, S, noise_for(S))
         ret = {"rgb_map": c["rgb"], "disp_map": c["disp"], "acc_map": c["acc"]}
 
@@ -444,7 +480,8 @@ class Renderer(torch.nn.Module):
                       "mofa_sample_pdf_merge")
             fine = network_fn if network_fine is None else network_fine
             folded = self._folded_coarse if network_fine is None else self._folded_fine
-            raw = network(fine, folded, z_fine, S + Ni, S + Ni)
+            raw = (network(fine, folded, z_fine, S + Ni, S + Ni) if occupancy is None else
+                   network_culled(fine, folded, z_fine, S + Ni, S + Ni, "fine"))
             f = composite(raw, z_fine, S + Ni, S + Ni, noise_for(S + Ni))
             ret = {"rgb_map": f["rgb"], "disp_map": f["disp"], "acc_map": f["acc"], "rgb0": c["rgb"],
                    "disp0": c["disp"], "acc0": c["acc"], "z_std": z_std}
@@ -454,6 +491,29 @@ class Renderer(torch.nn.Module):
         if retraw:
             ret["raw"] = raw
         return ret
+
+    def _check_occupancy(self, occupancy, rays, raw_noise_std, network_fn, network_fine):
+        """The refusals of occupancy-culled rendering (render_rays): each names its argument."""
+        from .occupancy import OccupancyGrid
+        if not isinstance(occupancy, OccupancyGrid):
+            raise lib.MofaError(f"occupancy: want an occupancy.OccupancyGrid (Renderer.build_occupancy / occupancy_from_grid), got "
+                                f"{type(occupancy).__name__}")
+        if not rays.is_cuda:
+            raise lib.MofaError("occupancy: the rays are CPU tensors; there is no CPU path")
+        if occupancy.device != rays.device:
+            raise lib.MofaError(f"occupancy: the grid lives on {occupancy.device}, the rays on {rays.device}")
+        if raw_noise_std > 0.:
+            raise lib.MofaError(f"raw_noise_std = {raw_noise_std} with occupancy: noise would give the skipped samples a density; "
+                                "culled rendering is for inference (raw_noise_std = 0)")
+        if torch.is_grad_enabled():
+            rg = lambda t: torch.is_tensor(t) and t.requires_grad
+            nets = [unwrap(n) for n in (network_fn, network_fine) if n is not None]
+            asks = (rg(rays) or rg(self.shapeCodes) or rg(self.decoding_texCodes) or rg(self.expCodes_Sigma[self.expType]) or
+                    any(q.requires_grad for q in unwrap(self.idSpecificMod).parameters()) or
+                    (self._weight_grads and any(q.requires_grad for n in nets for q in n.parameters())))
+            if asks:
+                raise lib.MofaError("occupancy: culled rendering is inference only, but autograd is enabled and a tensor (rays, codes, "
+                                    "StyleModule or network weights) asks for a gradient; render under torch.no_grad()")
 
     # ------------------------------------------------------------------------------------------------
     def _make_rays(self, H, W, K, c2w, rays, use_viewdirs, c2w_staticcam, ndc):
@@ -511,6 +571,7 @@ class Renderer(torch.nn.Module):
         self._rays_ref = self.rays          # (a reference, not an id: ids are reused after garbage collection)
         self._rays_version = self.rays._version
         self.decoding_texCodes = tex_code
+        self.occupancy_stats = None
         # inference (torch.no_grad(), as the reference's render-only call sites run): pure HIP, nothing recorded;
         # with autograd enabled (fitting / training) the tape-keeping forward + HIP backward path is used
         self._folded_coarse = self._fold_codes(kwargs["network_fn"], tex_code).clone()
@@ -659,6 +720,28 @@ class Renderer(torch.nn.Module):
                 out = out.reshape(res)
         self.check_launches(block=True)
         return out
+
+    def build_occupancy(self, networks, *, bounds, resolution, threshold, shapeCodes, expType=20, expCodes=None, dilate=1, netchunk=None):
+        """Occupancy grid for ``render_rays(..., occupancy=...)``: the density of each of ``networks`` (one network or a sequence,
+        normally coarse and fine) from :meth:`query_density` on the lattice ``bounds`` x ``resolution``; a cell is occupied iff one of
+        its 8 corner samples is ``> threshold`` in ANY of the networks (the union), and then iff a cell within Chebyshev distance
+        ``dilate`` (0 .. 8 cells) was (``occupancy.occupancy_from_grid``).  ``threshold`` has no default: no density level of a trained
+        MoFaNeRF has been measured.  Everything outside ``bounds`` counts as empty, so the bounds must hold the head.
+
+        The grid belongs to the shape and expression codes it was built with — density does not depend on the texture code, the view
+        direction or the camera pose (models/model.py:121-128), so one grid serves every frame of that identity and expression.  With
+        ``ndc=True`` the renderer's points are NDC points and ``bounds`` must be NDC bounds."""
+        from . import mesh, occupancy
+        nets = list(networks) if isinstance(networks, (list, tuple)) else [networks]
+        if not nets or any(n is None for n in nets):
+            raise lib.MofaError("build_occupancy: networks must be one network or a non-empty sequence of networks")
+        threshold = occupancy._check_threshold(threshold, "build_occupancy")
+        dilate = occupancy._check_dilate(dilate)
+        _, lo, step = mesh.grid_spec(bounds, resolution)
+        grids = [self.query_density(n, bounds=bounds, resolution=resolution, shapeCodes=shapeCodes, expType=expType, expCodes=expCodes,
+                                    netchunk=netchunk) for n in nets]
+        with torch.no_grad():
+            return occupancy.occupancy_from_grids(grids, threshold, lo, step, dilate)
 
     def extract_mesh(self, network, *, bounds, resolution, level, shapeCodes, expType=20, expCodes=None, uvCodes=None, colors=False,
                      netchunk=None, brick=None):
