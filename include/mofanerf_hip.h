@@ -62,7 +62,8 @@ int mofa_abi_version(void);
 const char* mofa_last_error(void);   /* thread-local text of the calling thread's last failure */
 
 /* Library-wide state is limited to what is listed here; everything else is in caller-owned buffers.
- *   - four run-time knobs, each choosing between BIT-IDENTICAL forms of the exact-fp32 path — MOFA_PIPE=0 (plain instead of
+ *   - five run-time knobs, each choosing between BIT-IDENTICAL forms of the exact-fp32 path — MOFA_GATE=0 (mofa_net_forward_gated runs the
+ *     full forward), MOFA_PIPE=0 (plain instead of
  *     software-pipelined K loops), MOFA_FUSED=0/1 (per-layer launches / persistent network kernel for widths <= 256), MOFA_CHAIN=0
  *     (per-layer launches instead of the chained launch of the wider networks), MOFA_CHAIN_TRAIN=1 (the TRAINING backward — products and
  *     weight gradients — as chained launches too; off by default: measured a tie); there is no reduced-precision
@@ -81,8 +82,12 @@ int mofa_config_reload(void);
  *                     starves an XCD looks like (an unworked tile queue -> NaN outputs + verdict "tiles missing").
  *   selfcheck_poison  non-zero: mofa_device_init()'s self-check sees one flipped bit in the chained result (forces its fallback). */
 int mofa_test_hooks(uint32_t chain_spin_limit, int32_t chain_skip_xcd, int32_t selfcheck_poison);
+/* TEST HOOK: non-zero = chain_spin_limit / chain_skip_xcd reach only the colour launch of mofa_net_forward_gated (the launch over a device-side
+ * row-tile count), so that its own verification can be seen to flag it; 0 restores the default (every chained launch). */
+int mofa_test_hooks_colour_only(int32_t on);
 
-/* Per-device initialisation — the ONE entry point that allocates (scratch of the checks below, ~70 MB, freed again) and synchronises
+/* Per-device initialisation — the ONE entry point that allocates (scratch of the checks below, ~70 MB, freed again; plus eight bytes kept
+ * per device: the measurement session's device-side FLOP sum, which mofa_prof_begin zeroes and mofa_prof_end reads) and synchronises
  * `stream`.  Call it once per device before the first mofa_net_forward (the shipped host layer does, when a network is bound to a
  * device).  It decides whether the wide networks of this device may take the chained launch (k_net_chain) — two checks, both needed:
  *   1. the XCD census: one tile queue per XCD, so all eight must receive workgroups of a 2-per-CU launch.
@@ -170,6 +175,23 @@ int mofa_net_forward(MofaNetShape s, const float* packed, const float* folded, c
                      const float* view_b, const float* rays_o, const float* rays_d, const float* z, int64_t z_row_stride,
                      const float* pts, const float* viewdirs, int64_t n_rays, int32_t S, float* workspace,
                      float* raw_out, float* tape, uint64_t* mask_tape, const float* view_bias_rows, uint32_t* verdict, void* stream);
+/* The sigma-gated forward (inference): mofa_net_forward's raw_out with the colour half of the network — texture stack, view layer, rgb
+ * head — run only for the samples whose raw density is not <= 0 (NaN counts as live).  A sample with sigma <= 0 has alpha = 0 and weight 0
+ * exactly, so compositing never sees its colour: raw_out[..., 3] holds mofa_net_forward's bits everywhere, raw_out[..., 0:3] holds them on
+ * the live samples and (0, 0, 0) on the others, and every composited output is the same bits.  Only the chained launch is gated: the geometry
+ * half over all rows, a 64-bit scan of the flags, a gather of the live rows' sigmaCodes and view-bias rows, a second chained launch over the
+ * live row tiles (a count that stays on the device), the rgb head and a scatter that writes every rgb element.  No tape, no host
+ * synchronisation, no allocation.  When the call would not take the chained launch (MOFA_CHAIN=0, MOFA_GATE=0, no or a failed
+ * mofa_device_init, widths the chain refuses, the persistent kernel of widths <= 256) it runs mofa_net_forward unchanged.
+ *   workspace: mofa_net_forward_gated_workspace_floats(s, n_rays*S, n_rays) floats, 16-byte aligned like raw_out — asked on the device
+ *   and under the knobs of the call: it is mofa_net_workspace_floats' figure when the call cannot gate there (knobs, shape, census).
+ *   stats: NULL, or two uint64 on the device: [0] += samples, [1] += live samples of every gated call (never read by the library).
+ *   gated: receives 1 (the gated route ran) or 0 (the full forward ran).  Everything else as for mofa_net_forward. */
+size_t mofa_net_forward_gated_workspace_floats(MofaNetShape s, int64_t n_points, int64_t n_rays);
+int mofa_net_forward_gated(MofaNetShape s, const float* packed, const float* folded, const float* view_w, const float* view_b,
+                           const float* rays_o, const float* rays_d, const float* z, int64_t z_row_stride, const float* pts,
+                           const float* viewdirs, int64_t n_rays, int32_t S, float* workspace, float* raw_out, const float* view_bias_rows,
+                           uint64_t* stats, int32_t* gated, uint32_t* verdict, void* stream);
 /* Density only — the geometry half of the network: sigma_out[n] = the pre-ReLU alpha head at explicit points pts [n,3], the SAME bits as
  * raw_out[..., 3] of mofa_net_forward on those points, whatever view directions and texture code that call had.  Density depends on the
  * point, the shape code and the expression code only (model.py:121-128): the launch stops after the linear_BiM_xyz stack — no texture

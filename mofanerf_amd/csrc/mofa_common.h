@@ -56,6 +56,7 @@ struct Config {
     int chain = -1;       // MOFA_CHAIN=0: per-layer launches for the wide networks instead of the chained launch (k_net_chain)
     int chain_train = -1; // MOFA_CHAIN_TRAIN=1: the TRAINING backward (products + weight gradients) as chained launches too (k_net_chain_train).
                           // Off by default: bit-identical, measured 0.2-0.4 % SLOWER than the per-layer launches it replaces
+    int gate = -1;        // MOFA_GATE=0: mofa_net_forward_gated runs the full forward (A/B and tests; the frame is the same bits either way)
 };
 const Config& config();
 
@@ -65,6 +66,7 @@ const Config& config();
 constexpr unsigned kChainSpinDefault = 1u << 22;   // polls (each >= ~1 us with its s_sleep) before a dependency wait gives up: seconds
 unsigned hook_chain_spin();        // polls before a dependency wait of k_net_chain gives up
 int hook_chain_skip_xcd();         // k_net_chain's workgroups on this XCD leave at once (an unworked queue); -1 = none
+int hook_colour_only();            // the two chain hooks above reach only launches over a device-side row count (the gated forward's colour half)
 int hook_selfcheck_poison();       // mofa_device_init's chained-vs-per-layer self-check sees one flipped bit (forces its fallback)
 
 constexpr int kMaxDevices = 64;

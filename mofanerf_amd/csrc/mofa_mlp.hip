@@ -23,9 +23,11 @@ namespace {
 template <int LD>
 __global__ __launch_bounds__(256) void k_head(const float* __restrict__ x, int kp, long long m_padded,
                                               const float* __restrict__ w, const float* __restrict__ b, int n_out,
-                                              float* __restrict__ raw, int raw_off, long long n_points) {
+                                              float* __restrict__ raw, int raw_off, long long n_points,
+                                              const long long* __restrict__ n_dev = nullptr) {
     const long long m = (long long)blockIdx.x * 256 + threadIdx.x;
     if (m >= n_points) return;
+    if (n_dev && m >= *n_dev) return;          // (the gated forward: rows past the device-side live count hold nothing)
     const int sw = (int)(m >> 2) & 3;
     const int K = kp * 16;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -861,6 +863,8 @@ struct ChainArgs {
     unsigned* state;
     long long m_padded, bias_rows;
     int m_tiles, n_steps, tiles_per_m;
+    const unsigned* live_tiles;       // NULL, or a device word holding the row tiles this launch really has (<= m_tiles: the gated forward's
+                                      // colour half runs over the compacted live rows, a count the host never sees); read once at entry
     unsigned spin_limit;              // polls (each >= ~1 us with its s_sleep) before a wait gives up: seconds, never a hang
     int skip_xcd;                     // tests only (mofa_test_hooks): workgroups on this XCD leave at once — what a CU-masked stream
                                       // that starves an XCD looks like; -1 = none
@@ -878,8 +882,11 @@ __global__ void k_xcc_census(unsigned* counts) {
 // overwritten with NaN (up to four buffers) and the sticky verdict words of the caller are raised:
 //   verdict[0] |= 1 (a wait timed out) | 2 (tiles missing);  [1] += 1 (launches verified);  [2], [3], [4] = this launch's flags,
 //   finished tiles, expected tiles;  [5] += 1 per bad launch.
+// live_tiles != NULL: the launch ran over a device-side row-tile count — expect = *live_tiles x per_tile (tiles of one row tile).
 __global__ __launch_bounds__(256) void k_chain_verify(const unsigned* __restrict__ status, unsigned expect, unsigned* __restrict__ verdict,
-                                                      float* p0, long long n0, float* p1, long long n1, float* p2, long long n2, float* p3, long long n3) {
+                                                      float* p0, long long n0, float* p1, long long n1, float* p2, long long n2, float* p3, long long n3,
+                                                      const unsigned* __restrict__ live_tiles, unsigned per_tile) {
+    if (live_tiles) expect = live_tiles[0] * per_tile;
     const unsigned flags = status[0], finished = status[1];
     const bool bad = flags != 0u || finished != expect;
     if (verdict && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -1034,9 +1041,10 @@ __global__ __launch_bounds__(256, 2) void k_net_chain(const ChainArgs a) {
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
     xcc &= 7u;
     if ((int)xcc == a.skip_xcd) return;
-    const int mpx = (a.m_tiles + 7) >> 3;
+    const int m_tiles = a.live_tiles ? __builtin_amdgcn_readfirstlane((int)a.live_tiles[0]) : a.m_tiles;     // (uniform: the eight queues split the LIVE row tiles evenly)
+    const int mpx = (m_tiles + 7) >> 3;
     const int m_lo = (int)xcc * mpx;
-    const int m_cnt = m_lo < a.m_tiles ? (a.m_tiles - m_lo < mpx ? a.m_tiles - m_lo : mpx) : 0;
+    const int m_cnt = m_lo < m_tiles ? (m_tiles - m_lo < mpx ? m_tiles - m_lo : mpx) : 0;
     const int total = m_cnt * a.tiles_per_m;
     unsigned* const head = a.state + xcc * kChainHeadStride;
     unsigned* const status = a.state + kChainStatus;
@@ -1364,6 +1372,13 @@ struct ProfState {
     double flops[kProfKinds] = {};
 };
 ProfState g_prof[kMaxDevices];
+// FLOPs of the chained launches whose row count only the device knows (the gated forward's colour half): summed on the device while a
+// session is open, read by mofa_prof_end behind its event waits.  One double per device, allocated by mofa_device_init (the library's
+// one allocating call) and kept for the life of the process.
+double* g_prof_dev[kMaxDevices];
+__global__ void k_prof_add_tiles(double* acc, const unsigned* __restrict__ live_tiles, double flops_per_tile) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) atomicAdd(acc, (double)live_tiles[0] * flops_per_tile);
+}
 std::atomic<bool> g_prof_on[kMaxDevices];
 std::mutex g_prof_mu;
 
@@ -1605,6 +1620,14 @@ int mofa_head_forward(const float* x, int32_t k_padded, int64_t m_padded, const 
     return check_launch("k_head");
 }
 
+// internal (used by mofa_net.hip): mofa_head_forward over the first *n_dev (a device word, <= n_points) rows only — the gated forward's rgb head
+int mofa_internal_head_counted(const float* x, int32_t k_padded, int64_t m_padded, const float* w_dense, const float* b, int32_t n_out,
+                               float* raw_out, int32_t raw_off, int64_t n_points, const long long* n_dev, void* stream) {
+    hipLaunchKernelGGL(k_head<4>, dim3(blocks_for(n_points)), dim3(256), 0, (hipStream_t)stream, x, k_padded / 16, (long long)m_padded, w_dense, b,
+                       n_out, raw_out, raw_off, (long long)n_points, n_dev);
+    return check_launch("k_head");
+}
+
 // internal (used by mofa_net.hip): the alpha head of the density form — out[m] = sigmaCodes[m] . w + b, the value mofa_head_forward
 // writes into raw[m][3], bit for bit
 int mofa_internal_head_dense(const float* x, int32_t k_padded, int64_t m_padded, const float* w_dense, const float* b, float* out,
@@ -1638,6 +1661,7 @@ int mofa_prof_begin(void) {
     ProfState& P = g_prof[dev];
     P.used = 0;
     for (int k = 0; k < kProfKinds; ++k) P.flops[k] = 0.0;
+    if (g_prof_dev[dev] && hipMemset(g_prof_dev[dev], 0, sizeof(double)) != hipSuccess) return check_launch("hipMemset(prof)");
     g_prof_on[dev].store(true, std::memory_order_relaxed);
     return MOFA_OK;
 }
@@ -1658,6 +1682,13 @@ int mofa_prof_end(double* total_ms, int64_t* launches, double* padded_flops) {
         total_ms[P.kind[i]] += (double)t, launches[P.kind[i]] += 1;
     }
     for (int k = 0; k < kProfKinds; ++k) padded_flops[k] = P.flops[k];
+    if (g_prof_dev[dev]) {       // the row tiles the gated launches really executed (kind 5), never their upper bound
+        double live = 0.0;
+        // (the sums are enqueued behind the timed brackets: wait for the device, not only for the events)
+        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&live, g_prof_dev[dev], sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+            return check_launch("hipMemcpy(prof)");
+        padded_flops[5] += live;
+    }
     P.used = 0;
     return MOFA_OK;
 }
@@ -1733,6 +1764,7 @@ int mofa_device_init(void* stream, int32_t* xcd_workgroups, int32_t* chain_selfc
         set_error("device_init: %s", hipGetErrorString(e));
         return MOFA_EHIP;
     }
+    if (dev == current_device() && !g_prof_dev[dev] && hipMalloc((void**)&g_prof_dev[dev], sizeof(double)) != hipSuccess) return check_launch("hipMalloc(profiler accumulator)");
     int populated = 0;
     for (int i = 0; i < 8; ++i) {
         populated += host[i] > 0;
@@ -1771,16 +1803,20 @@ int mofa_internal_chain_capable(void* stream) {
 // mofa_internal_chain_state_words(m_padded) unsigned words inside the caller's workspace.  *tiles_out = tiles the launch must finish.
 size_t mofa_internal_chain_state_words(long long m_padded) { return (size_t)kChainDone + (size_t)(m_padded / kRowTile) + 32; }
 
-int mofa_internal_chain_launch(int mode, const mofa::ChainStep* steps, int n_steps, long long m_padded, long long bias_rows, unsigned* state,
-                               long long* tiles_out, void* stream) {
+// live_tiles: NULL, or a device word with the row tiles the launch really has (at most m_padded / 256, which sizes everything the host
+// sizes: the grid, the state, the panel stride); *tiles_out is then the tiles of ONE row tile (mofa_internal_chain_verify_live).
+static int chain_launch(int mode, const mofa::ChainStep* steps, int n_steps, long long m_padded, long long bias_rows, unsigned* state,
+                        long long* tiles_out, const unsigned* live_tiles, void* stream) {
     MOFA_REQUIRE(n_steps > 0 && n_steps <= kMaxChainSteps, "chain_launch: %d steps (max %d)", n_steps, kMaxChainSteps);
     MOFA_REQUIRE(m_padded > 0 && m_padded % kRowTile == 0 && m_padded / kRowTile < (1 << 24), "chain_launch: m_padded=%lld", m_padded);
     MOFA_REQUIRE(steps && state && mode >= kChainForward && mode <= kChainBackward, "chain_launch: bad arguments");
     ChainArgs a{};
     a.state = state;
     a.m_padded = m_padded, a.bias_rows = bias_rows, a.m_tiles = (int)(m_padded / kRowTile), a.n_steps = n_steps;
-    a.spin_limit = hook_chain_spin();         // (the shipped values unless a TEST called mofa_test_hooks(): nothing in the environment)
-    a.skip_xcd = hook_chain_skip_xcd();
+    a.live_tiles = live_tiles;
+    const bool hooked = live_tiles || !hook_colour_only();
+    a.spin_limit = hooked ? hook_chain_spin() : kChainSpinDefault;         // (the shipped values unless a TEST called mofa_test_hooks(): nothing in the environment)
+    a.skip_xcd = hooked ? hook_chain_skip_xcd() : -1;
     double flops = 0.0;
     int before = 0;
     for (int i = 0; i < n_steps; ++i) {
@@ -1803,7 +1839,7 @@ int mofa_internal_chain_launch(int mode, const mofa::ChainStep* steps, int n_ste
     if (hipMemsetAsync(state, 0, mofa_internal_chain_state_words(m_padded) * sizeof(unsigned), st) != hipSuccess) return check_launch("hipMemsetAsync(chain state)");
     const int dev = stream_device(st);
     const long long tiles = (long long)a.m_tiles * before;
-    if (tiles_out) *tiles_out = tiles;
+    if (tiles_out) *tiles_out = live_tiles ? (long long)before : tiles;
     const int slots = 2 * compute_units(dev);
     const int grid = tiles < slots ? (int)round_up(tiles, 8) : slots;       // two resident workgroups per CU
     const size_t lds = 2 * (size_t)(kRowTile + 128) * 16 * sizeof(float) + 64;
@@ -1813,8 +1849,22 @@ int mofa_internal_chain_launch(int mode, const mofa::ChainStep* steps, int n_ste
     if (mode == kChainForward) hipLaunchKernelGGL(k_net_chain<kChainForward>, dim3(grid), dim3(256), lds, st, a);
     else if (mode == kChainForwardMask) hipLaunchKernelGGL(k_net_chain<kChainForwardMask>, dim3(grid), dim3(256), lds, st, a);
     else hipLaunchKernelGGL(k_net_chain<kChainBackward>, dim3(grid), dim3(256), lds, st, a);
-    if (prof) prof_close(st, pkind, flops);
+    if (prof) prof_close(st, pkind, live_tiles ? 0.0 : flops);
+    // a launch over a device-side row count: the FLOPs of the row tiles executed are summed on the device, behind the timed bracket
+    // (mofa_prof_end reads the sum; the accumulator is mofa_device_init's, without which no chained launch is taken)
+    if (prof && live_tiles && g_prof_dev[dev])
+        hipLaunchKernelGGL(k_prof_add_tiles, dim3(1), dim3(64), 0, st, g_prof_dev[dev], live_tiles, flops / (double)a.m_tiles);
     return check_launch("k_net_chain");
+}
+
+int mofa_internal_chain_launch(int mode, const mofa::ChainStep* steps, int n_steps, long long m_padded, long long bias_rows, unsigned* state,
+                               long long* tiles_out, void* stream) {
+    return chain_launch(mode, steps, n_steps, m_padded, bias_rows, state, tiles_out, nullptr, stream);
+}
+int mofa_internal_chain_launch_live(int mode, const mofa::ChainStep* steps, int n_steps, long long m_padded, long long bias_rows, unsigned* state,
+                                    long long* tiles_per_m_out, const unsigned* live_tiles, void* stream) {
+    MOFA_REQUIRE(live_tiles, "chain_launch_live: null pointer");
+    return chain_launch(mode, steps, n_steps, m_padded, bias_rows, state, tiles_per_m_out, live_tiles, stream);
 }
 
 // internal (used by mofa_net.hip): the steps of one chained TRAINING-backward launch (k_net_chain_train): backward-data products and weight
@@ -1886,7 +1936,17 @@ int mofa_internal_chain_verify(const unsigned* state, long long tiles, unsigned*
     long long grid = (n + 255) / 256;
     grid = grid < 1 ? 1 : (grid > 1024 ? 1024 : grid);
     hipLaunchKernelGGL(k_chain_verify, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, state + kChainStatus, (unsigned)tiles, verdict, p0, n0, p1,
-                       n1, p2, n2, p3, n3);
+                       n1, p2, n2, p3, n3, (const unsigned*)nullptr, 0u);
+    return check_launch("k_chain_verify");
+}
+
+// internal (used by mofa_net.hip): the same behind a launch over a device-side row-tile count: expected tiles = *live_tiles x tiles_per_m
+int mofa_internal_chain_verify_live(const unsigned* state, const unsigned* live_tiles, long long tiles_per_m, unsigned* verdict, float* p0, long long n0,
+                                    void* stream) {
+    long long grid = (n0 + 255) / 256;
+    grid = grid < 1 ? 1 : (grid > 1024 ? 1024 : grid);
+    hipLaunchKernelGGL(k_chain_verify, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, state + kChainStatus, 0u, verdict, p0, p0 ? n0 : 0,
+                       (float*)nullptr, 0ll, (float*)nullptr, 0ll, (float*)nullptr, 0ll, live_tiles, (unsigned)tiles_per_m);
     return check_launch("k_chain_verify");
 }
 

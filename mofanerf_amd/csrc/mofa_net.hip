@@ -41,6 +41,14 @@ int mofa_internal_chain_train_launch(const mofa::ChainStep* steps, int n_steps, 
 int mofa_internal_chain_poison(const unsigned* state, long long tiles, float* const* ptrs, const long long* sizes, int count, void* stream);
 int mofa_internal_head_dense(const float* x, int32_t k_padded, int64_t m_padded, const float* w_dense, const float* b, float* out,
                               int64_t n_points, void* stream);
+int mofa_internal_chain_launch_live(int mode, const mofa::ChainStep* steps, int n_steps, long long m_padded, long long bias_rows, unsigned* state,
+                                    long long* tiles_per_m_out, const unsigned* live_tiles, void* stream);
+int mofa_internal_chain_verify_live(const unsigned* state, const unsigned* live_tiles, long long tiles_per_m, unsigned* verdict, float* p0, long long n0,
+                                    void* stream);
+int mofa_internal_head_counted(const float* x, int32_t k_padded, int64_t m_padded, const float* w_dense, const float* b, int32_t n_out,
+                               float* raw_out, int32_t raw_off, int64_t n_points, const long long* n_dev, void* stream);
+long long mofa_internal_scan_aux(long long n);
+int mofa_internal_scan_bytes(const unsigned char* in, long long n, long long* out, long long* aux, void* stream);
 int mofa_internal_wgrad_reduce(const float* partial, int splits, int n_padded, int k_padded, int n_out, int ncols, float* dst, int ld,
                                int col0, float* bias_out, void* stream);
 }
@@ -62,11 +70,13 @@ Config read_env() {
     Config c;
     auto tri = [](const char* name) { const char* e = getenv(name); return e ? (e[0] == '1' ? 1 : 0) : -1; };
     c.fused = tri("MOFA_FUSED"), c.pipe = tri("MOFA_PIPE"), c.chain = tri("MOFA_CHAIN"), c.chain_train = tri("MOFA_CHAIN_TRAIN");
+    c.gate = tri("MOFA_GATE");
     return c;
 }
 std::atomic<unsigned> g_hook_spin{kChainSpinDefault};
 std::atomic<int> g_hook_skip_xcd{-1};
 std::atomic<int> g_hook_poison{0};
+std::atomic<int> g_hook_colour_only{0};
 // two slots + an atomic index: readers never see a half-written snapshot, reload is rare and host-side only
 Config g_cfg[2] = {read_env(), Config{}};
 std::atomic<int> g_cfg_cur{0};
@@ -77,6 +87,7 @@ const Config& config() { return g_cfg[g_cfg_cur.load(std::memory_order_acquire)]
 unsigned hook_chain_spin() { return g_hook_spin.load(std::memory_order_relaxed); }
 int hook_chain_skip_xcd() { return g_hook_skip_xcd.load(std::memory_order_relaxed); }
 int hook_selfcheck_poison() { return g_hook_poison.load(std::memory_order_relaxed); }
+int hook_colour_only() { return g_hook_colour_only.load(std::memory_order_relaxed); }
 
 int current_device() {
     int dev = 0;
@@ -253,6 +264,99 @@ __global__ __launch_bounds__(256) void k_selfcheck_compare(const unsigned* __res
 }
 __global__ void k_selfcheck_poison(unsigned* p) { p[0] ^= 1u; }
 
+// ---- the sigma-gated forward (mofa_net_forward_gated): what sits between its two chained launches -----------------------------------
+// A sample whose raw density is <= 0 has alpha = 1 - exp(-relu(sigma) dist) = 0 and weight 0 exactly, so its colour never reaches a pixel:
+// the texture stack, the view layer and the rgb head run over the LIVE rows only, compacted in ascending order through the 64-bit scan of
+// the flags (no atomics: the same input gives the same bytes).  The host never learns the count: it stays in device words.
+struct GateLayout {          // offsets in floats behind the ordinary workspace, each on a 256-byte boundary
+    size_t vb, rgb, scan, aux, flags, counts, state, total;
+};
+// Would a forward of this shape take the gated route — by the knobs, the dispatch rule (never the persistent kernel), the chain's tile
+// forms and the device's census?  Necessary for gating (net_forward also asks its own step list) and what sizes the workspace: a call
+// that cannot gate needs mofa_net_forward's buffers only.
+bool gate_wanted(const Plan& p, int64_t n_points, void* stream) {
+    const Config& cfg = config();
+    if (cfg.gate == 0 || cfg.chain == 0 || cfg.pipe == 0) return false;
+    const int64_t mp = round_up(n_points, kRowTile);
+    if (cfg.fused >= 0 ? cfg.fused == 1 : (p.Wp <= 256 && mp / kRowTile >= 128)) return false;
+    int mfma = 0;
+    for (const Layer& l : p.L) {
+        if (l.head) continue;
+        const int kt = l.k_padded[0] / 16 + (l.nsrc > 1 ? l.k_padded[1] / 16 : 0);
+        if (l.n_padded % 128 != 0 || kt < 4 || (kt & 1)) return false;
+        ++mfma;
+    }
+    if (mfma > MOFA_MAX_CHAIN_STEPS || p.L[p.xyz0].n_padded < 512) return false;
+    return mofa_internal_chain_capable(stream) == 1;
+}
+
+GateLayout gate_layout(const Plan& p, int64_t n_points, int64_t n_rays, MofaNetShape s) {
+    const size_t mp = (size_t)round_up(n_points, kRowTile);
+    auto r64 = [](size_t v) { return (size_t)round_up((int64_t)v, 64); };
+    GateLayout g;
+    g.vb = r64(mofa_net_workspace_floats(s, n_points, n_rays));      // per-point bias rows of the view layer [Mp][Hp]
+    g.rgb = g.vb + mp * (size_t)p.Hp;                                  // the rgb head's values of the compacted rows [Mp][4]
+    g.scan = g.rgb + mp * 4;                                           // exclusive scan of the flags [Mp] (64-bit)
+    g.aux = g.scan + mp * 2;                                           // the scan's block sums
+    g.flags = g.aux + r64((size_t)mofa_internal_scan_aux(n_points) * 2);
+    g.counts = g.flags + r64(mp / 4);                                  // [0..1] live rows (64-bit), [2] live row tiles
+    g.state = g.counts + 64;                                           // queue state of the colour launch
+    g.total = g.state + r64(mofa_internal_chain_state_words((long long)mp));
+    return g;
+}
+
+__global__ __launch_bounds__(256) void k_gate_flags(const float* __restrict__ raw, long long n, unsigned char* __restrict__ flags) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e < n) flags[e] = !(raw[e * 4 + 3] <= 0.0f) ? 1 : 0;          // (NaN is live: a non-finite density still reaches the frame)
+}
+// counts: the live rows and their row tiles; stats (optional): += {samples, live samples}
+__global__ void k_gate_count(const long long* __restrict__ scan, const unsigned char* __restrict__ flags, long long n, long long* __restrict__ n_live,
+                             unsigned* __restrict__ live_tiles, unsigned long long* __restrict__ stats) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const long long live = scan[n - 1] + flags[n - 1];
+    n_live[0] = live;
+    live_tiles[0] = (unsigned)((live + kRowTile - 1) / kRowTile);
+    if (stats) atomicAdd(stats, (unsigned long long)n), atomicAdd(stats + 1, (unsigned long long)live);
+}
+// One lane per sample; blockIdx.y strides over kp + hp / 16 slices of 16 floats.  Slice b < kp: panel b of a live row's sigmaCodes moves
+// from row e to row j = scan[e] (the panels' quad swizzle follows the row: (row / 4) % 4); the slices behind copy the row's per-ray view
+// bias into the per-point bias rows.
+__global__ __launch_bounds__(256) void k_gate_gather(const float* __restrict__ x, float* __restrict__ xc, long long m_padded, int kp,
+                                                     const float* __restrict__ vbias, float* __restrict__ vbc, int hp, int S,
+                                                     const unsigned char* __restrict__ flags, const long long* __restrict__ scan, long long n) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n || !flags[e]) return;
+    const long long j = scan[e], r = e / S;
+    const int se = (int)(e >> 2) & 3, sj = (int)(j >> 2) & 3;
+    for (int b = blockIdx.y; b < kp + hp / 16; b += gridDim.y) {
+        if (b < kp) {
+            const f32x4* src = (const f32x4*)(x + ((long long)b * m_padded + e) * 16);
+            f32x4* dst = (f32x4*)(xc + ((long long)b * m_padded + j) * 16);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) dst[c ^ sj] = src[c ^ se];
+        } else {
+            const f32x4* src = (const f32x4*)(vbias + r * hp + (b - kp) * 16);
+            f32x4* dst = (f32x4*)(vbc + j * hp + (b - kp) * 16);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) dst[c] = src[c];
+        }
+    }
+}
+// every rgb element of raw: the head's value of the row's slot for a live sample, zeros for a dead one (sigma stays)
+__global__ __launch_bounds__(256) void k_gate_scatter(const f32x4* __restrict__ rgbc, const long long* __restrict__ scan, long long n,
+                                                      f32x4* __restrict__ raw) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    f32x4 v = raw[e];
+    if (!(v.w <= 0.0f)) {
+        const f32x4 c = rgbc[scan[e]];
+        v.x = c.x, v.y = c.y, v.z = c.z;
+    } else {
+        v.x = v.y = v.z = 0.0f;
+    }
+    raw[e] = v;
+}
+
 #define MOFA_SHAPE_FMT "D=%d W=%d multires=%d multires_views=%d ch_exp=%d ch_shape=%d ch_tex=%d"
 #define MOFA_SHAPE_ARGS(s) (s).D, (s).W, (s).pe_point_freqs, (s).pe_view_freqs, (s).ch_exp, (s).ch_shape, (s).ch_tex
 
@@ -278,6 +382,11 @@ int mofa_test_hooks(uint32_t chain_spin_limit, int32_t chain_skip_xcd, int32_t s
     g_hook_spin.store(chain_spin_limit ? chain_spin_limit : kChainSpinDefault, std::memory_order_relaxed);
     g_hook_skip_xcd.store(chain_skip_xcd, std::memory_order_relaxed);
     g_hook_poison.store(selfcheck_poison ? 1 : 0, std::memory_order_relaxed);
+    return MOFA_OK;
+}
+
+int mofa_test_hooks_colour_only(int32_t on) {
+    g_hook_colour_only.store(on ? 1 : 0, std::memory_order_relaxed);
     return MOFA_OK;
 }
 
@@ -388,6 +497,12 @@ int mofa_net_pack_t(MofaNetShape s, const float* const* weights, float* packed_t
 #define MOFA_TRY(expr) \
     if ((rc = (expr)) != MOFA_OK) return rc
 
+// what mofa_net_forward_gated adds to a forward call
+struct GateCall {
+    unsigned long long* stats;     // NULL, or device accumulators {samples, live samples}
+    int32_t* route;                // receives 1 (gated) / 0 (the full forward ran)
+};
+
 // force_chain: -1 = by configuration + census (every caller but the self-check); 0 = the per-layer launches, 1 = the chained launch —
 // whatever MOFA_* says and whatever the census found (mofa_device_init's self-check runs both forms on the same inputs)
 // sigma_out != NULL: the DENSITY form (mofa_net_density) — the step list stops after the shape stack (sigmaCodes), there is no texture
@@ -397,7 +512,7 @@ static int net_forward(MofaNetShape s, const float* packed, const float* folded,
                        const float* view_b, const float* rays_o, const float* rays_d, const float* z, int64_t z_row_stride,
                        const float* pts, const float* viewdirs, int64_t n_rays, int32_t S, float* workspace,
                        float* raw_out, float* tape, uint64_t* mask_tape, const float* view_bias_rows, uint32_t* verdict, void* stream,
-                       int force_chain, float* sigma_out = nullptr) {
+                       int force_chain, float* sigma_out = nullptr, const GateCall* gate = nullptr) {
     const bool density = sigma_out != nullptr;
     MOFA_REQUIRE(shape_ok(s), "net_forward: unsupported shape " MOFA_SHAPE_FMT, MOFA_SHAPE_ARGS(s));
     MOFA_REQUIRE(packed && folded && workspace && (raw_out || density), "net_forward: null pointer");
@@ -459,6 +574,7 @@ static int net_forward(MofaNetShape s, const float* packed, const float* folded,
         return const_cast<float*>(cur);
     };
     float* sigma = cond(p.bim0, p.bim_skip, xyz, bufB, t0, t1);
+    const size_t n_geo = steps.size();                              // steps of the geometry half (up to sigmaCodes)
     float* v = nullptr;
     if (!density) {                                                 // (density: sigmaCodes is all the alpha head reads)
         float* rgbc = cond(p.uv0, p.uv_skip, sigma, bufA, t0, t1);  // without a tape rgbCodes reuses xyz_code's buffer
@@ -518,6 +634,60 @@ static int net_forward(MofaNetShape s, const float* packed, const float* folded,
         if (mask_tape) {  // the view layer's per-ray-bias epilogue is not the contiguous-store one: its bits come from a pass over its output
             MOFA_TRY(mofa_internal_mask_pack(v, (long long)Mp * p.L[p.view].n_padded, mbits + mword(p.view), stream));
         }
+    } else if (gate && !tape && !mask_tape && gate_wanted(p, M, stream) && chain_ok()) {
+        // The sigma-gated forward: the geometry half over every row, flags + scan of (sigma > 0 or NaN), the colour half over the live rows.
+        // Two chained launches of the same tiles (a row's values do not depend on where the row sits in a batch: bit-identical).
+        // The colour steps are the full forward's with bufA and bufB exchanged: they read the COMPACTED sigmaCodes the gather leaves in
+        // bufA (xyz_code is dead by then) and leave rgbCodes in bufB (sigmaCodes is dead once the alpha head and the gather have read it).
+        auto colour = [&](const float* q) -> float* { return const_cast<float*>(q == bufA ? bufB : (q == bufB ? bufA : q)); };
+        const GateLayout gl = gate_layout(p, M, n_rays, s);
+        float* vbc = workspace + gl.vb;
+        float* rgbc4 = workspace + gl.rgb;
+        long long* scan = (long long*)(workspace + gl.scan);
+        long long* aux = (long long*)(workspace + gl.aux);
+        unsigned char* flags = (unsigned char*)(workspace + gl.flags);
+        long long* n_live = (long long*)(workspace + gl.counts);
+        unsigned* live_tiles = (unsigned*)(workspace + gl.counts) + 2;
+        unsigned* state2 = (unsigned*)(workspace + gl.state);
+        hipStream_t hs = (hipStream_t)stream;
+        MOFA_TRY(mofa_pe_panels(rays_o, rays_d, z, z_row_stride, pts, M, S, s.pe_point_freqs, Mp, t1, stream));
+        std::vector<ChainStep> cs(steps.size());
+        for (size_t i = 0; i < steps.size(); ++i) {
+            const Layer& l = p.L[steps[i].li];
+            const bool view = steps[i].li == p.view;
+            ChainStep c{};
+            c.x1 = steps[i].x1 ? steps[i].x1 : t1, c.x2 = steps[i].x2, c.y = steps[i].y;
+            if (i >= n_geo) c.x1 = colour(c.x1), c.x2 = colour(c.x2), c.y = colour(c.y);
+            c.w = packed + l.packed_off, c.aux = view ? vbc : folded + l.folded_off;     // (one bias row per compacted point)
+            c.k1p = l.k_padded[0] / 16, c.k2p = steps[i].x2 ? l.k_padded[1] / 16 : 0;
+            c.n_padded = l.n_padded, c.bias_row_div = view ? 1 : 0, c.flags = 1;
+            cs[i] = c;
+        }
+        chain_state = (unsigned*)(vbias + (size_t)n_rays * p.Hp + 64);
+        long long tiles2 = 0;
+        MOFA_TRY(mofa_internal_chain_launch(kChainForward, cs.data(), (int)n_geo, Mp, n_rays, chain_state, &chain_tiles, stream));
+        const Layer& la = p.L[p.alpha];
+        MOFA_TRY(mofa_head_forward(sigma, la.k_padded[0], Mp, packed + la.packed_off, folded + la.folded_off, 1, raw_out, 3, M, stream));
+        const unsigned blocks = (unsigned)((M + 255) / 256);
+        hipLaunchKernelGGL(k_gate_flags, dim3(blocks), dim3(256), 0, hs, (const float*)raw_out, (long long)M, flags);
+        MOFA_TRY(check_launch("k_gate_flags"));
+        MOFA_TRY(mofa_internal_scan_bytes(flags, M, scan, aux, stream));
+        hipLaunchKernelGGL(k_gate_count, dim3(1), dim3(64), 0, hs, (const long long*)scan, (const unsigned char*)flags, (long long)M, n_live,
+                           live_tiles, gate->stats);
+        hipLaunchKernelGGL(k_gate_gather, dim3(blocks, 8), dim3(256), 0, hs, (const float*)sigma, bufA,
+                           (long long)Mp, p.Wp / 16, view_bias_rows, vbc, p.Hp, (int)S, (const unsigned char*)flags,
+                           (const long long*)scan, (long long)M);
+        MOFA_TRY(check_launch("k_gate_gather"));
+        MOFA_TRY(mofa_internal_chain_launch_live(kChainForward, cs.data() + n_geo, (int)(cs.size() - n_geo), Mp, Mp, state2, &tiles2, live_tiles,
+                                                 stream));
+        const Layer& lr = p.L[p.rgb];
+        MOFA_TRY(mofa_internal_head_counted(v, lr.k_padded[0], Mp, packed + lr.packed_off, folded + lr.folded_off, 3, rgbc4, 0, M, n_live, stream));
+        hipLaunchKernelGGL(k_gate_scatter, dim3(blocks), dim3(256), 0, hs, (const f32x4*)rgbc4, (const long long*)scan, (long long)M, (f32x4*)raw_out);
+        MOFA_TRY(check_launch("k_gate_scatter"));
+        MOFA_TRY(mofa_internal_chain_verify(chain_state, chain_tiles, verdict, raw_out, M * 4, nullptr, 0, nullptr, 0, nullptr, 0, stream));
+        MOFA_TRY(mofa_internal_chain_verify_live(state2, live_tiles, tiles2, verdict, raw_out, M * 4, stream));
+        *gate->route = 1;
+        return MOFA_OK;
     } else if (chain_ok()) {
         // Wide network: ONE chained launch (k_net_chain, mofa_mlp.hip) over the tiles of every layer — the same tiles as the per-layer
         // launches below (bit-identical), without their ~26 launch boundaries per sub-batch.  Layer 0 reads the encoding panels
@@ -592,6 +762,25 @@ int mofa_net_forward(MofaNetShape s, const float* packed, const float* folded, c
                      float* raw_out, float* tape, uint64_t* mask_tape, const float* view_bias_rows, uint32_t* verdict, void* stream) {
     return net_forward(s, packed, folded, view_w, view_b, rays_o, rays_d, z, z_row_stride, pts, viewdirs, n_rays, S, workspace, raw_out, tape,
                        mask_tape, view_bias_rows, verdict, stream, -1);
+}
+
+size_t mofa_net_forward_gated_workspace_floats(MofaNetShape s, int64_t n_points, int64_t n_rays) {
+    if (!shape_ok(s) || n_points <= 0 || n_rays <= 0) return 0;
+    const Plan p = make_plan(s);
+    if (!gate_wanted(p, n_points, nullptr)) return mofa_net_workspace_floats(s, n_points, n_rays);     // (the full forward will run)
+    return gate_layout(p, n_points, n_rays, s).total;
+}
+
+int mofa_net_forward_gated(MofaNetShape s, const float* packed, const float* folded, const float* view_w, const float* view_b,
+                           const float* rays_o, const float* rays_d, const float* z, int64_t z_row_stride, const float* pts,
+                           const float* viewdirs, int64_t n_rays, int32_t S, float* workspace, float* raw_out, const float* view_bias_rows,
+                           uint64_t* stats, int32_t* gated, uint32_t* verdict, void* stream) {
+    MOFA_REQUIRE(gated, "net_forward_gated: null pointer");
+    MOFA_REQUIRE(((uintptr_t)raw_out & 15) == 0 && ((uintptr_t)workspace & 15) == 0, "net_forward_gated: raw_out and workspace must be 16-byte aligned");
+    *gated = 0;
+    const GateCall g{(unsigned long long*)stats, gated};
+    return net_forward(s, packed, folded, view_w, view_b, rays_o, rays_d, z, z_row_stride, pts, viewdirs, n_rays, S, workspace, raw_out, nullptr,
+                       nullptr, view_bias_rows, verdict, stream, -1, nullptr, &g);
 }
 
 int mofa_net_density(MofaNetShape s, const float* packed, const float* folded, const float* pts, int64_t n_points, float* workspace,

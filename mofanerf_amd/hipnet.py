@@ -87,6 +87,8 @@ class HipNet:
         self._packed_t_key = None
         self._bws: Optional[torch.Tensor] = None
         self._nominal, self._nominal_key = None, None
+        self.gate_stats_dev: Optional[torch.Tensor] = None   # [2] int64 on the device: samples / live samples of the gated calls
+        self.last_gated: Optional[int] = None                 # route of the last gated call: 1 = gated, 0 = the full forward ran
 
     @property
     def net(self) -> Optional[NeRF]:
@@ -279,16 +281,45 @@ class HipNet:
             raise lib.MofaError(f"expression / shape / texture code widths {got} do not match the network's {want} "
                                 f"(input_ch - (3 + 6*multires), input_ch_shapeCodes, input_ch_textureCodes of {self.shape})")
 
-    def workspace(self, n_points: int, n_rays: int, device, slot: int = 0) -> torch.Tensor:
+    def workspace(self, n_points: int, n_rays: int, device, slot: int = 0, floats: Optional[int] = None) -> torch.Tensor:
         """Activation buffers of one sub-batch.  ``slot`` > 0: an independent buffer for a sub-batch that runs concurrently on
         another stream."""
-        n = self._L.mofa_net_workspace_floats(self.shape, n_points, n_rays)
+        n = self._L.mofa_net_workspace_floats(self.shape, n_points, n_rays) if floats is None else int(floats)
         if self._ws is None:
             self._ws = {}
         ws = self._ws.get(slot)
         if ws is None or ws.numel() < n or ws.device != device:
             ws = self._ws[slot] = torch.empty(n, dtype=torch.float32, device=device)
         return ws
+
+    def gate_stats_buffer(self, device) -> torch.Tensor:
+        """The device-side counters of the gated calls, created zeroed on first use — on the CALLER's stream: whoever forks side streams
+        calls this first, so that no side stream zero-fills what another already adds to."""
+        if self.gate_stats_dev is None or self.gate_stats_dev.device != device:
+            self.gate_stats_dev = torch.zeros(2, dtype=torch.int64, device=device)
+        return self.gate_stats_dev
+
+    def _forward_gated(self, rays_o, rays_d, z, z_row_stride, pts, viewdirs, R, S, raw_out, folded, slot, snapshot):
+        import ctypes as C
+        view = self._linears[-3]
+        dev = viewdirs.device
+        # the SAME per-slot buffer as the full forward's, grown only when this call can gate (the library sizes it by the route it will take)
+        with torch.cuda.device(dev):
+            ws = self.workspace(R * S, R, dev, slot, floats=self._L.mofa_net_forward_gated_workspace_floats(self.shape, R * S, R))
+        stats = self.gate_stats_buffer(dev)
+        route = C.c_int32(0)
+        self.check_verdict()
+        lib.check(self._L.mofa_net_forward_gated(self.shape, lib.ptr(self.packed()),
+                                                 lib.ptr(folded if folded is not None else self._folded),
+                                                 lib.ptr(view.weight.detach().contiguous()), lib.ptr(view.bias.detach().contiguous()),
+                                                 lib.ptr(rays_o), lib.ptr(rays_d), lib.ptr(z), z_row_stride, lib.ptr(pts),
+                                                 lib.ptr(viewdirs), R, S, lib.ptr(ws), lib.ptr(raw_out), None,
+                                                 stats.data_ptr(), C.byref(route), self.verdict_ptr(dev), lib.stream()),
+                  "mofa_net_forward_gated")
+        self.last_gated = int(route.value)
+        if snapshot:
+            self.snapshot_verdict()
+        return raw_out
 
     # -- NeRF.forward on ALREADY-EMBEDDED per-point inputs (the reference module's own call form) ---------------
     def _nominal_pack(self):
@@ -413,11 +444,14 @@ class HipNet:
 
     # -- forward -----------------------------------------------------------------------------------
     def forward_rays(self, rays_o, rays_d, z, z_row_stride: int, viewdirs, S: int, raw_out: torch.Tensor,
-                     folded: Optional[torch.Tensor] = None, slot: int = 0, snapshot: bool = True):
+                     folded: Optional[torch.Tensor] = None, slot: int = 0, snapshot: bool = True, gate: bool = False):
         """raw_out[R,S,4] = NeRF(PE(o + d z), codes, PE(viewdirs)) for R rays x S samples.  ``snapshot=False``: a call on a SIDE
         stream — the caller snapshots the verdict words itself, on the main stream, once it has joined the side streams (two streams
-        writing the one pinned mirror could overwrite a raised flag with an older, clean copy)."""
+        writing the one pinned mirror could overwrite a raised flag with an older, clean copy).  ``gate=True``: the sigma-gated forward
+        (``mofa_net_forward_gated``) — the same sigma everywhere, rgb = 0 where sigma <= 0: for callers that only composite ``raw_out``."""
         R = viewdirs.shape[0]
+        if gate:
+            return self._forward_gated(rays_o, rays_d, z, z_row_stride, None, viewdirs, R, S, raw_out, folded, slot, snapshot)
         view = self._linears[-3]
         ws = self.workspace(R * S, R, viewdirs.device, slot)
         self.check_verdict()
@@ -432,9 +466,11 @@ class HipNet:
             self.snapshot_verdict()
         return raw_out
 
-    def forward_points(self, pts, viewdirs, S: int, raw_out: torch.Tensor, folded: Optional[torch.Tensor] = None):
-        """Same with explicit points [R*S,3] (``run_network(inputs, viewdirs, fn)`` entry)."""
+    def forward_points(self, pts, viewdirs, S: int, raw_out: torch.Tensor, folded: Optional[torch.Tensor] = None, gate: bool = False):
+        """Same with explicit points [R*S,3] (``run_network(inputs, viewdirs, fn)`` entry); ``gate`` as for :meth:`forward_rays`."""
         R = viewdirs.shape[0]
+        if gate:
+            return self._forward_gated(None, None, None, 0, pts, viewdirs, R, S, raw_out, folded, 0, True)
         view = self._linears[-3]
         ws = self.workspace(R * S, R, viewdirs.device)
         self.check_verdict()

@@ -42,6 +42,7 @@ SIGNATURES = {
     "mofa_last_error": (C.c_char_p, []),
     "mofa_config_reload": (C.c_int, []),
     "mofa_test_hooks": (C.c_int, [C.c_uint32, _i32, _i32]),
+    "mofa_test_hooks_colour_only": (C.c_int, [_i32]),
     "mofa_device_init": (C.c_int, [_fp, C.POINTER(_i32), C.POINTER(_i32)]),
     "mofa_net_num_layers": (C.c_int, [NetShape]),
     "mofa_net_layer_dims": (C.c_int, [NetShape, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
@@ -53,6 +54,9 @@ SIGNATURES = {
     "mofa_net_fold": (C.c_int, [NetShape, C.POINTER(_fp), C.POINTER(_fp), _fp, _fp, _fp, _fp, _fp]),
     "mofa_net_forward": (C.c_int, [NetShape, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _fp, _fp, _i64, _i32, _fp, _fp,
                                    _fp, _fp, _fp, _fp, _fp]),
+    "mofa_net_forward_gated_workspace_floats": (_sz, [NetShape, _i64, _i64]),
+    "mofa_net_forward_gated": (C.c_int, [NetShape, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _fp, _fp, _i64, _i32, _fp, _fp, _fp, _fp,
+                                         C.POINTER(_i32), _fp, _fp]),
     "mofa_net_density": (C.c_int, [NetShape, _fp, _fp, _fp, _i64, _fp, _fp, _fp, _fp]),
     "mofa_grid_points": (C.c_int, [_i64, _i64, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), _i64, _i64, _fp, _fp]),
     "mofa_iso_workspace_bytes": (_sz, [_i64, _i64, _i64]),
@@ -194,8 +198,10 @@ def chain_selfcheck(device=None) -> int:
     return _device_selfcheck[torch.cuda.current_device() if idx is None else idx]
 
 
-def test_hooks(chain_spin_limit: int = 0, chain_skip_xcd: int = -1, selfcheck_poison: bool = False) -> None:
-    """``mofa_test_hooks`` (tests / tools only): force the chained launch's failure paths.  Defaults restore the shipped behaviour."""
+def test_hooks(chain_spin_limit: int = 0, chain_skip_xcd: int = -1, selfcheck_poison: bool = False, colour_only: bool = False) -> None:
+    """``mofa_test_hooks`` (tests / tools only): force the chained launch's failure paths.  Defaults restore the shipped behaviour.
+    ``colour_only``: the two chain hooks reach only the colour launch of the sigma-gated forward (``mofa_test_hooks_colour_only``)."""
+    check(load().mofa_test_hooks_colour_only(int(bool(colour_only))), "mofa_test_hooks_colour_only")
     check(load().mofa_test_hooks(int(chain_spin_limit), int(chain_skip_xcd), int(bool(selfcheck_poison))), "mofa_test_hooks")
 
 

@@ -200,6 +200,18 @@ class Renderer(torch.nn.Module):
                 look()
         return check
 
+    def gate_stats(self, reset: bool = False):
+        """Samples and live samples (raw sigma not <= 0) of the sigma-gated forwards so far, per bound network: ``{(D, W): {"samples",
+        "live"}}``.  Reads device-side accumulators (one host synchronisation, here and nowhere on the render path): for tools."""
+        out = {}
+        for h in list(self._hipnets.values()):
+            if h.gate_stats_dev is not None:
+                n, live = (int(v) for v in h.gate_stats_dev.tolist())
+                out[(h.D, h.W)] = {"samples": n, "live": live}
+                if reset:
+                    h.gate_stats_dev.zero_()
+        return out
+
     def check_launches(self, block: bool = True):
         """Raise ``MofaError`` if any chained launch issued through this renderer ended incomplete (the kernel abandons a launch rather
         than compute on incomplete inputs, and a verification kernel then overwrites the outputs with NaN — see
@@ -381,6 +393,9 @@ class Renderer(torch.nn.Module):
             return (torch.randn(R, n_s, device=dev) * raw_noise_std).contiguous()
 
         grad = torch.is_grad_enabled()
+        # the sigma-gated forward (colour half only where sigma > 0): whenever nothing but compositing reads raw — noise would change
+        # which samples are dead, and retraw hands raw to the caller
+        gate = not grad and not raw_noise_std > 0. and not retraw
 
         def composite(raw, zv, zs, n_s, noise):
             if grad:
@@ -411,11 +426,13 @@ class Renderer(torch.nn.Module):
             if n_str <= 1:
                 for i in starts:
                     j = min(R, i + rays_per)
-                    h.forward_rays(rays_o[i:j], rays_d[i:j], zv[i:j] if zs else zv, zs, vd[i:j], n_s, raw[i:j], folded)
+                    h.forward_rays(rays_o[i:j], rays_d[i:j], zv[i:j] if zs else zv, zs, vd[i:j], n_s, raw[i:j], folded, gate=gate)
                 return raw
             # Independent sub-batches round-robin over a few streams: kernels of different streams are not in step with each
             # other, so one stream's launch boundaries (tail, write burst, first fetches) are filled by the others' workgroups.
             h.packed()                                              # (re)pack on the main stream, before the side streams fork
+            if gate:
+                h.gate_stats_buffer(dev)                            # (likewise: created and zeroed before any side stream adds to it)
             main = torch.cuda.current_stream(dev)
             side = self._side_streams(n_str, dev)
             for s_ in side:
@@ -424,7 +441,7 @@ class Renderer(torch.nn.Module):
                 j = min(R, i + rays_per)
                 with torch.cuda.stream(side[k % n_str]):
                     h.forward_rays(rays_o[i:j], rays_d[i:j], zv[i:j] if zs else zv, zs, vd[i:j], n_s, raw[i:j], folded,
-                                   slot=k % n_str, snapshot=False)
+                                   slot=k % n_str, snapshot=False, gate=gate)
             for s_ in side:
                 main.wait_stream(s_)
             h.snapshot_verdict()       # ONE snapshot, on the main stream, behind every side stream's launches
@@ -446,7 +463,7 @@ class Renderer(torch.nn.Module):
                 raw_kept = torch.empty(cp.n_kept, 1, 4, dtype=torch.float32, device=dev)
                 per = max(1, int(self.netchunk))
                 for i in range(0, cp.n_kept, per):
-                    h.forward_points(pts[i:i + per], dirs[i:i + per], 1, raw_kept[i:i + per], folded)
+                    h.forward_points(pts[i:i + per], dirs[i:i + per], 1, raw_kept[i:i + per], folded, gate=gate)
             return cp.scatter(raw_kept, raw)
 
         if occupancy is not None:
