@@ -303,6 +303,12 @@ int mofa_occ_gather(const float* rays_o, const float* rays_d, const float* viewd
 int mofa_occ_scatter(const float* raw_kept, const uint8_t* flags, const void* workspace, int64_t n_samples, int64_t n_kept, float* raw,
                      void* stream);
 
+/* The one-float twin of mofa_occ_scatter (the geometry-only render): sigma [n_samples] = sigma_kept [n_kept] entry scan[e] for a kept
+ * sample, 0 for a skipped one; every element is written by this one kernel, a slot at or beyond n_kept gives NaN.  sigma_kept may be NULL
+ * when n_kept = 0. */
+int mofa_occ_scatter_sigma(const float* sigma_kept, const uint8_t* flags, const void* workspace, int64_t n_samples, int64_t n_kept,
+                           float* sigma, void* stream);
+
 /* ---- backward (run_fit.py:305-313 photometric fitting, run_train.py:333-357 training) -----------------------
  * Backward of mofa_net_forward given d_raw [n_rays,S,4] and the tape (fp32, or mask-only when d_weights == NULL) of that forward:
  *   d_folded  [mofa_net_folded_floats]: gradient w.r.t. every folded bias (sum over points of the ReLU-masked
@@ -439,6 +445,20 @@ int mofa_rays_pose_backward(int32_t W, float fx, float fy, float cx, float cy, c
 int mofa_composite_forward(const float* raw, const float* z, int64_t z_row_stride, const float* rays_d,
                            const float* noise, int64_t n_rays, int32_t S, int32_t white_bkgd, float* rgb,
                            float* disp, float* acc, float* depth, float* weights, void* stream);
+
+/* ---- geometry-only render: depth, silhouette and disparity from the density alone ---------------------------
+ * pts [n_rays*S,3]: pts[r S + s] = o_r + d_r * z_{r,s}, the multiply and the add rounded separately — the point mofa_net_forward forms
+ * in its layer-0 prologue and mofa_occ_gather forms for a kept sample; what mofa_net_density takes.  z [n_rays,S] (z_row_stride = S) or
+ * one shared row (stride 0); at least one and fewer than 2^31 samples. */
+int mofa_ray_points(const float* rays_o, const float* rays_d, const float* z, int64_t z_row_stride, int64_t n_rays, int32_t S,
+                    float* pts, void* stream);
+
+/* raw2outputs without colour: sigma [n_rays,S] is the pre-ReLU density (raw[..., 3]) on its own; noise may be NULL.  Writes disp, acc,
+ * depth [n_rays] and weights [n_rays,S] (required: the resampler's input) — each the same bits mofa_composite_forward gives for a raw
+ * whose channel 3 is sigma (same lane-to-sample assignment, same operations in the same order).  S >= 2, z_row_stride 0 or S, fewer
+ * than 2^31 samples. */
+int mofa_composite_sigma(const float* sigma, const float* z, int64_t z_row_stride, const float* rays_d, const float* noise,
+                         int64_t n_rays, int32_t S, float* disp, float* acc, float* depth, float* weights, void* stream);
 
 /* sample_pdf on (z_mid, weights[1:-1]) + sort(cat(z, z_samples)) + std(z_samples)
  * (render_class.py:324-328,345; tools/run_nerf_helpers.py:203-247).  u: [n_rays,Ni] (stride Ni) or a

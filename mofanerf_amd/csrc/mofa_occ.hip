@@ -9,7 +9,7 @@
 //   per axis   t = (p - lo) / step (correctly rounded);  inside = t >= 0 && t <= (float)(n - 1) (false for NaN);  c = min((int)t, n - 2)
 //   kept       inside on all three axes and the cell occupied
 //
-// Kernels: k_occ_cells, k_occ_dilate_axis, k_occ_classify, k_occ_total, k_occ_gather, k_occ_scatter.  One lane per cell / sample.
+// Kernels: k_occ_cells, k_occ_dilate_axis, k_occ_classify, k_occ_total, k_occ_gather, k_occ_scatter, k_occ_scatter_sigma.  One lane per cell / sample.
 #include <math.h>
 
 #include "mofa_common.h"
@@ -134,6 +134,20 @@ __global__ __launch_bounds__(256) void k_occ_scatter(const f32x4* __restrict__ r
     raw[e] = v;
 }
 
+// the one-float twin (the geometry-only render): every element of sigma, the network's density for a kept sample, zero for a skipped one
+__global__ __launch_bounds__(256) void k_occ_scatter_sigma(const float* __restrict__ sigma_kept, const unsigned char* __restrict__ flags,
+                                                           const long long* __restrict__ scan, long long n_samples, long long n_kept,
+                                                           float* __restrict__ sigma) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_samples) return;
+    float v = 0.0f;
+    if (flags[e]) {
+        const long long k = scan[e];
+        v = k < n_kept ? sigma_kept[k] : __builtin_nanf("");
+    }
+    sigma[e] = v;
+}
+
 }  // namespace
 }  // namespace mofa
 
@@ -222,6 +236,18 @@ int mofa_occ_scatter(const float* raw_kept, const uint8_t* flags, const void* wo
     hipLaunchKernelGGL(k_occ_scatter, dim3(blocks_of(n_samples)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)raw_kept,
                        (const unsigned char*)flags, (const long long*)workspace, (long long)n_samples, (long long)n_kept, (f32x4*)raw);
     return check_launch("k_occ_scatter");
+}
+
+int mofa_occ_scatter_sigma(const float* sigma_kept, const uint8_t* flags, const void* workspace, int64_t n_samples, int64_t n_kept,
+                           float* sigma, void* stream) {
+    MOFA_REQUIRE(flags && workspace && sigma, "occ_scatter_sigma: null pointer");
+    MOFA_REQUIRE(n_samples >= 1 && n_samples < kOccMaxSamples, "occ_scatter_sigma: %lld samples", (long long)n_samples);
+    MOFA_REQUIRE(n_kept >= 0 && n_kept <= n_samples && (n_kept == 0 || sigma_kept),
+                 "occ_scatter_sigma: n_kept = %lld of %lld samples (sigma_kept %s)", (long long)n_kept, (long long)n_samples,
+                 sigma_kept ? "given" : "NULL");
+    hipLaunchKernelGGL(k_occ_scatter_sigma, dim3(blocks_of(n_samples)), dim3(256), 0, (hipStream_t)stream, sigma_kept,
+                       (const unsigned char*)flags, (const long long*)workspace, (long long)n_samples, (long long)n_kept, sigma);
+    return check_launch("k_occ_scatter_sigma");
 }
 
 }  // extern "C"

@@ -243,6 +243,157 @@ __global__ __launch_bounds__(256) void k_composite_long(const float* __restrict_
     }
 }
 
+// ---- raw2outputs without colour: depth / acc / disp / weights from the density alone ------------------------------------------
+// The geometry-only render's compositing (mofa_composite_sigma).  `sigma [n_rays,S]` is raw[..., 3] (pre-ReLU) on its own.  Same
+// lane-to-sample assignment, same operations in the same order as k_composite / k_composite_long — dist * dnorm, relu, 1 - expf(-sig * dist),
+// the in-lane running product, the 6-step prefix product, wave_sum, __fdiv_rn, the NaN rule — so every output is the bits
+// mofa_composite_forward gives for a raw whose channel 3 is sigma (no multiply-add is fused in this translation unit).
+template <int SPL>
+__global__ __launch_bounds__(256) void k_composite_sigma(const float* __restrict__ sigma, const float* __restrict__ z,
+                                                         long long z_row_stride, const float* __restrict__ rays_d,
+                                                         const float* __restrict__ noise, long long n_rays, int S,
+                                                         float* __restrict__ disp_out, float* __restrict__ acc_out,
+                                                         float* __restrict__ depth_out, float* __restrict__ weights_out) {
+    const int lane = threadIdx.x & 63;
+    const long long ray = (long long)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const float dx = rays_d[ray * 3], dy = rays_d[ray * 3 + 1], dz = rays_d[ray * 3 + 2];
+    const float dnorm = __fsqrt_rn(dx * dx + dy * dy + dz * dz);
+    const float* zr = z + ray * z_row_stride;
+    const float* sr = sigma + ray * (long long)S;
+
+    float zv[SPL + 1], alpha[SPL];
+    const int s0 = lane * SPL;
+#pragma unroll
+    for (int t = 0; t <= SPL; ++t) zv[t] = (s0 + t < S) ? zr[s0 + t] : 0.f;
+    float run = 1.0f;  // product of this lane's (1 - alpha + 1e-10)
+#pragma unroll
+    for (int t = 0; t < SPL; ++t) {
+        const int s = s0 + t;
+        if (s < S) {
+            float dist = (s + 1 < S) ? (zv[t + 1] - zv[t]) : 1e10f;
+            dist = dist * dnorm;
+            float sig = sr[s];
+            if (noise) sig = sig + noise[ray * (long long)S + s];
+            sig = relu_np(sig);
+            alpha[t] = 1.0f - expf(-sig * dist);
+            run = run * ((1.0f - alpha[t]) + 1e-10f);
+        } else {
+            alpha[t] = 0.f;
+        }
+    }
+    // exclusive prefix product across lanes
+    float incl = run;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl = incl * up;
+    }
+    float T = __shfl_up(incl, 1, 64);
+    if (lane == 0) T = 1.0f;
+
+    float sd = 0.f, sa = 0.f;
+#pragma unroll
+    for (int t = 0; t < SPL; ++t) {
+        const int s = s0 + t;
+        if (s < S) {
+            const float w = alpha[t] * T;
+            weights_out[ray * (long long)S + s] = w;
+            sd += w * zv[t];
+            sa += w;
+            T = T * ((1.0f - alpha[t]) + 1e-10f);
+        }
+    }
+    sd = wave_sum(sd), sa = wave_sum(sa);
+    if (lane == 0) {
+        const float q = __fdiv_rn(sd, sa);  // 0/0 -> NaN, as in k_composite
+        disp_out[ray] = (q != q) ? q : __fdiv_rn(1.0f, fmaxf(1e-10f, q));
+        acc_out[ray] = sa;
+        depth_out[ray] = sd;
+    }
+}
+
+// more than 256 samples: k_composite_long's passes of 256 samples (lane l owns samples [256 p + 4 l, +4) of pass p)
+__global__ __launch_bounds__(256) void k_composite_sigma_long(const float* __restrict__ sigma, const float* __restrict__ z,
+                                                              long long z_row_stride, const float* __restrict__ rays_d,
+                                                              const float* __restrict__ noise, long long n_rays, int S,
+                                                              float* __restrict__ disp_out, float* __restrict__ acc_out,
+                                                              float* __restrict__ depth_out, float* __restrict__ weights_out) {
+    constexpr int SPL = 4;
+    const int lane = threadIdx.x & 63;
+    const long long ray = (long long)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const float dx = rays_d[ray * 3], dy = rays_d[ray * 3 + 1], dz = rays_d[ray * 3 + 2];
+    const float dnorm = __fsqrt_rn(dx * dx + dy * dy + dz * dz);
+    const float* zr = z + ray * z_row_stride;
+    const float* sr = sigma + ray * (long long)S;
+    float carry = 1.0f;                                   // transmittance in front of the current pass
+    float sd = 0.f, sa = 0.f;
+    for (int base = 0; base < S; base += 64 * SPL) {
+        float zv[SPL + 1], alpha[SPL];
+        const int s0 = base + lane * SPL;
+#pragma unroll
+        for (int t = 0; t <= SPL; ++t) zv[t] = (s0 + t < S) ? zr[s0 + t] : 0.f;
+        float run = 1.0f;
+#pragma unroll
+        for (int t = 0; t < SPL; ++t) {
+            const int s = s0 + t;
+            if (s < S) {
+                float dist = (s + 1 < S) ? (zv[t + 1] - zv[t]) : 1e10f;
+                dist = dist * dnorm;
+                float sig = sr[s];
+                if (noise) sig = sig + noise[ray * (long long)S + s];
+                sig = relu_np(sig);
+                alpha[t] = 1.0f - expf(-sig * dist);
+                run = run * ((1.0f - alpha[t]) + 1e-10f);
+            } else {
+                alpha[t] = 0.f;
+            }
+        }
+        float incl = run;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float up = __shfl_up(incl, o, 64);
+            if (lane >= o) incl = incl * up;
+        }
+        float T = __shfl_up(incl, 1, 64);
+        if (lane == 0) T = 1.0f;
+        T = carry * T;
+        carry = carry * __shfl(incl, 63, 64);
+#pragma unroll
+        for (int t = 0; t < SPL; ++t) {
+            const int s = s0 + t;
+            if (s < S) {
+                const float w = alpha[t] * T;
+                weights_out[ray * (long long)S + s] = w;
+                sd += w * zv[t];
+                sa += w;
+                T = T * ((1.0f - alpha[t]) + 1e-10f);
+            }
+        }
+    }
+    sd = wave_sum(sd), sa = wave_sum(sa);
+    if (lane == 0) {
+        const float q = __fdiv_rn(sd, sa);
+        disp_out[ray] = (q != q) ? q : __fdiv_rn(1.0f, fmaxf(1e-10f, q));
+        acc_out[ray] = sa;
+        depth_out[ray] = sd;
+    }
+}
+
+// ---- the points of a pass: p = o + d * z, multiply and add rounded separately (the point the network's layer-0 prologue forms) ----
+__global__ __launch_bounds__(256) void k_ray_points(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                    const float* __restrict__ z, long long z_row_stride, long long n_samples, int S,
+                                                    float* __restrict__ pts) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_samples) return;
+    const long long r = e / S;
+    const int s = (int)(e - r * S);
+    const float zv = z[r * z_row_stride + s];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) pts[e * 3 + a] = __fadd_rn(rays_o[r * 3 + a], __fmul_rn(rays_d[r * 3 + a], zv));
+}
+
 // ---- sample_pdf + sort(cat) + std (tools/run_nerf_helpers.py:203-247; render_class.py:324-328,345) ----
 // One wavefront per ray.  B = S-1 bin edges z_mid, B-1 = S-2 interior weights.
 // cdf follows the CPU reference: cumsum accumulates in double and rounds every prefix to float.
@@ -434,6 +585,42 @@ int mofa_composite_forward(const float* raw, const float* z, int64_t z_row_strid
 #undef MOFA_COMPOSITE
     if (prof) mofa_internal_prof_close(stream, pkind, (double)n_rays);
     return check_launch("k_composite");
+}
+
+int mofa_composite_sigma(const float* sigma, const float* z, int64_t z_row_stride, const float* rays_d, const float* noise,
+                         int64_t n_rays, int32_t S, float* disp, float* acc, float* depth, float* weights, void* stream) {
+    MOFA_REQUIRE(sigma && z && rays_d && disp && acc && depth && weights, "composite_sigma: null pointer");
+    MOFA_REQUIRE(n_rays > 0 && S >= 2, "composite_sigma: need S >= 2 (got %d)", S);
+    MOFA_REQUIRE(z_row_stride == 0 || z_row_stride == S, "composite_sigma: z_row_stride = %lld with S = %d (want 0 or S)",
+                 (long long)z_row_stride, (int)S);
+    MOFA_REQUIRE(n_rays < (1ll << 31) && n_rays * (int64_t)S < (1ll << 31), "composite_sigma: %lld rays x %d samples (want fewer than 2^31 samples)",
+                 (long long)n_rays, (int)S);
+    const dim3 grid(blocks_for(n_rays, kWavesPerBlock)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define MOFA_COMPOSITE_SIGMA(SPL)                                                                                         \
+    hipLaunchKernelGGL((k_composite_sigma<SPL>), grid, block, 0, st, sigma, z, (long long)z_row_stride, rays_d, noise, \
+                       (long long)n_rays, S, disp, acc, depth, weights)
+    if (S <= 64) MOFA_COMPOSITE_SIGMA(1);
+    else if (S <= 128) MOFA_COMPOSITE_SIGMA(2);
+    else if (S <= 256) MOFA_COMPOSITE_SIGMA(4);
+    else
+        hipLaunchKernelGGL(k_composite_sigma_long, grid, block, 0, st, sigma, z, (long long)z_row_stride, rays_d, noise, (long long)n_rays, S,
+                           disp, acc, depth, weights);
+#undef MOFA_COMPOSITE_SIGMA
+    return check_launch("k_composite_sigma");
+}
+
+int mofa_ray_points(const float* rays_o, const float* rays_d, const float* z, int64_t z_row_stride, int64_t n_rays, int32_t S,
+                    float* pts, void* stream) {
+    MOFA_REQUIRE(rays_o && rays_d && z && pts, "ray_points: null pointer");
+    MOFA_REQUIRE(n_rays >= 1 && S >= 1 && n_rays < (1ll << 31) && n_rays * (int64_t)S < (1ll << 31),
+                 "ray_points: %lld rays x %d samples (want at least one and fewer than 2^31 samples)", (long long)n_rays, (int)S);
+    MOFA_REQUIRE(z_row_stride == 0 || z_row_stride == S, "ray_points: z_row_stride = %lld with S = %d (want 0 or S)",
+                 (long long)z_row_stride, (int)S);
+    const long long n = (long long)n_rays * S;
+    hipLaunchKernelGGL(k_ray_points, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, z,
+                       (long long)z_row_stride, n, (int)S, pts);
+    return check_launch("k_ray_points");
 }
 
 int mofa_sample_pdf_merge(const float* z, int64_t z_row_stride, const float* weights, const float* u,

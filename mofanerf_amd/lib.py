@@ -77,6 +77,7 @@ SIGNATURES = {
                                     _fp, _fp, _fp]),
     "mofa_occ_gather": (C.c_int, [_fp, _fp, _fp, _fp, _i64, _i64, _i32, _fp, _fp, _i64, _fp, _fp, _fp, _fp]),
     "mofa_occ_scatter": (C.c_int, [_fp, _fp, _fp, _i64, _i64, _fp, _fp]),
+    "mofa_occ_scatter_sigma": (C.c_int, [_fp, _fp, _fp, _i64, _i64, _fp, _fp]),
     "mofa_net_packed_t_floats": (_sz, [NetShape]),
     "mofa_net_tape_floats": (_sz, [NetShape, _i64]),
     "mofa_net_mask_tape_words": (_sz, [NetShape, _i64]),
@@ -118,6 +119,8 @@ SIGNATURES = {
     "mofa_get_rays_at": (C.c_int, [_i32, _i32, C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp, _i64, _fp, _fp, _fp, _fp]),
     "mofa_rays_pose_backward": (C.c_int, [_i32, C.c_float, C.c_float, C.c_float, C.c_float, _fp, _i64, _i64, _fp, _fp, _fp, _fp]),
     "mofa_composite_forward": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _i64, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "mofa_ray_points": (C.c_int, [_fp, _fp, _fp, _i64, _i64, _i32, _fp, _fp]),
+    "mofa_composite_sigma": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _i64, _i32, _fp, _fp, _fp, _fp, _fp]),
     "mofa_sample_pdf_merge": (C.c_int, [_fp, _i64, _fp, _fp, _i64, _i64, _i32, _i32, _fp, _fp, _fp, _fp]),
     "mofa_sample_pdf": (C.c_int, [_fp, _i64, _fp, _fp, _i64, _i64, _i32, _i32, _fp, _fp]),
 }

@@ -106,7 +106,8 @@ def occupancy_from_grid(grid: torch.Tensor, threshold, lo, step, dilate: int = 1
 class CulledPass:
     """One pass (coarse or fine) of ``R`` rays x ``S`` samples classified against a grid: ``flags [R,S]`` (uint8), ``n_kept`` (the pass's
     one host read), and — after :meth:`gather` — the kept samples' points, view directions and flat sample indices ``r S + s`` in
-    ascending order.  :meth:`scatter` writes every element of ``raw [R,S,4]``."""
+    ascending order.  :meth:`scatter` writes every element of ``raw [R,S,4]``,
+    :meth:`scatter_sigma` every element of a one-float ``sigma [R,S]``."""
 
     def __init__(self, grid: OccupancyGrid, rays_o, rays_d, z, z_stride: int, S: int):
         L = lib.load()
@@ -143,6 +144,13 @@ class CulledPass:
         lib.check(lib.load().mofa_occ_scatter(lib.ptr(raw_kept) if self.n_kept else None, self.flags.data_ptr(), self._ws.data_ptr(),
                                               self.n_samples, self.n_kept, lib.ptr(raw), lib.stream()), "mofa_occ_scatter")
         return raw
+
+
+    def scatter_sigma(self, sigma_kept, sigma: torch.Tensor) -> torch.Tensor:
+        """``sigma [R,S]``: the entries of ``sigma_kept [n_kept]`` at the kept samples, zeros elsewhere (the geometry-only render)."""
+        lib.check(lib.load().mofa_occ_scatter_sigma(lib.ptr(sigma_kept) if self.n_kept else None, self.flags.data_ptr(), self._ws.data_ptr(),
+                                                    self.n_samples, self.n_kept, lib.ptr(sigma), lib.stream()), "mofa_occ_scatter_sigma")
+        return sigma
 
 
 __all__: Sequence[str] = ("OccupancyGrid", "occupancy_from_grid", "occupancy_from_grids", "CulledPass", "MAX_DILATE")

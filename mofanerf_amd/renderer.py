@@ -738,6 +738,153 @@ class Renderer(torch.nn.Module):
         self.check_launches(block=True)
         return out
 
+    _GEOMETRY_READS = ("network_fn", "network_fine", "N_samples", "N_importance", "perturb", "lindisp", "pytest", "raw_noise_std")
+    _GEOMETRY_IGNORES = ("white_bkgd", "use_viewdirs", "retraw", "network_query_fn", "verbose")     # none of them changes geometry
+
+    def render_geometry(self, H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., shapeCodes=None, expType=20,
+                        expCodes=None, c2w_staticcam=None, occupancy=None, retweights=False, **render_kwargs):
+        """Geometry-only render: ``depth, disp, acc, extras`` of a frame from the density alone — no texture stack, no view layer, no rgb
+        head, one float per sample instead of four.  Takes the ``render_kwargs_test`` dictionary the scripts hand to
+        :meth:`render_fitting` (``network_fn``, ``network_fine``, ``N_samples``, ``N_importance``, ``perturb``, ``lindisp``, ``pytest``
+        are read; ``white_bkgd``, ``use_viewdirs``, ``retraw``, ``network_query_fn`` and ``verbose`` change no geometry and are
+        ignored; ``raw_noise_std > 0`` and unknown keys are refused).  There is no texture argument: the texture code never reaches the
+        density (models/model.py:121-128).
+
+        Everything geometric in a frame depends on density alone (render_class.py:440-482), so ``disp``, ``acc``, the coarse ``disp0`` /
+        ``acc0`` and ``z_std`` are the bits :meth:`render_fitting` returns for the same rays and codes, and ``depth`` / ``weights`` the bits
+        ``mofa_composite_forward`` computes inside it and drops.  Per pass: ``mofa_ray_points`` on sub-batches of ``netchunk`` points,
+        ``HipNet.density_points``, ``mofa_composite_sigma``; between the passes ``mofa_sample_pdf_merge`` as in :meth:`render_rays`.
+        ``occupancy`` (an ``occupancy.OccupancyGrid``): the density runs on the kept samples only, as in the culled :meth:`render_rays`
+        (``self.occupancy_stats`` is filled the same way).  ``extras``: ``depth0``, ``disp0``, ``acc0``, ``z_std`` when a fine pass ran;
+        with ``retweights=True`` also ``weights`` and ``z_vals`` of the final pass.  Inference only: runs under ``torch.no_grad()`` on
+        detached inputs.  No host synchronisation apart from the culled passes' kept counts; ``frame_check`` / ``check_launches`` work
+        afterwards as for :meth:`render`."""
+        for k in render_kwargs:
+            if k not in self._GEOMETRY_READS and k not in self._GEOMETRY_IGNORES:
+                raise lib.MofaError(f"render_geometry: unknown argument {k!r} (reads {', '.join(self._GEOMETRY_READS)}; ignores "
+                                    f"{', '.join(self._GEOMETRY_IGNORES)})")
+        noise_std = render_kwargs.get("raw_noise_std", 0.)
+        if noise_std is not None and _scalar(noise_std) > 0.:
+            raise lib.MofaError(f"render_geometry: raw_noise_std = {_scalar(noise_std)}: density noise is a training regulariser; the "
+                                "geometry render is for inference (raw_noise_std = 0)")
+        if render_kwargs.get("network_fn") is None or render_kwargs.get("N_samples") is None:
+            raise lib.MofaError("render_geometry: network_fn and N_samples are required (pass the render_kwargs_test dictionary)")
+        network_fn, network_fine = render_kwargs["network_fn"], render_kwargs.get("network_fine")
+        S, Ni = int(render_kwargs["N_samples"]), int(render_kwargs.get("N_importance", 0) or 0)
+        perturb, lindisp, pytest = render_kwargs.get("perturb", 0.), bool(render_kwargs.get("lindisp", False)), bool(render_kwargs.get("pytest", False))
+        L = self._lib()
+        with torch.no_grad():
+            rays_o, rays_d, viewdirs, sh = self._make_rays(H, W, K, c2w, rays, True, c2w_staticcam, ndc)
+            if c2w is None and not (rays[0].is_cuda and rays[1].is_cuda):
+                raise lib.MofaError("render_geometry: the rays are CPU tensors; there is no CPU path")
+            rays_o, rays_d, viewdirs = (t.detach().float().contiguous() for t in (rays_o, rays_d, viewdirs))
+            dev, n_rays = rays_o.device, int(rays_o.shape[0])
+            per_ray = lambda v: torch.is_tensor(v) and v.numel() > 1 or isinstance(v, np.ndarray) and v.size > 1
+            col = lambda v: torch.as_tensor(v, dtype=torch.float32).detach().reshape(-1, 1).to(dev) * torch.ones_like(rays_d[..., :1])
+            scalar_bounds = not per_ray(near) and not per_ray(far)
+            if scalar_bounds:       # one shared row of sample positions, built on the host as render_rays builds it
+                near, far = _scalar(near), _scalar(far)
+            else:
+                ncol, fcol = (col(v) if per_ray(v) else _scalar(v) * torch.ones_like(rays_d[..., :1]) for v in (near, far))
+            self._set_codes(shapeCodes, expType, expCodes)
+            self.occupancy_stats = None
+            if occupancy is not None:
+                self._check_occupancy(occupancy, rays_o, 0., network_fn, network_fine)
+                self.occupancy_stats = {}
+            fine_pass = Ni > 0 and self.is_run_fineNet
+            fine = network_fn if network_fine is None else network_fine
+            nets = [network_fn] + ([fine] if fine_pass and fine is not network_fn else [])
+            # the texture code feeds only the uv layers, which a density query does not run: zeros fold as well as any code
+            folded = {id(n): self._fold_codes(n, torch.zeros(self._hip(n).ch_tex, dtype=torch.float32, device=dev)).clone() for n in nets}
+            st = lib.stream()
+            out: Dict[str, list] = {}
+            for b0 in range(0, n_rays, int(chunk)):
+                ro, rd, vd = rays_o[b0:b0 + chunk], rays_d[b0:b0 + chunk], viewdirs[b0:b0 + chunk]
+                R = int(ro.shape[0])
+                t_row = self._const_row(("t", S), lambda: torch.linspace(0., 1., steps=S), dev)
+                if scalar_bounds:
+                    def z_row():
+                        t = torch.linspace(0., 1., steps=S)
+                        n, f = torch.tensor([[near]]), torch.tensor([[far]])
+                        z = n * (1. - t) + f * t if not lindisp else 1. / (1. / n * (1. - t) + 1. / f * t)
+                        return z.reshape(-1)
+
+                    z, z_stride = self._const_row(("z", near, far, S, lindisp), z_row, dev), 0
+                else:
+                    n, f = ncol[b0:b0 + chunk], fcol[b0:b0 + chunk]
+                    z = (n * (1. - t_row) + f * t_row if not lindisp else 1. / (1. / n * (1. - t_row) + 1. / f * t_row)).contiguous()
+                    z_stride = S
+                if perturb > 0.:
+                    zz = z[None, :].expand(R, S) if z_stride == 0 else z
+                    mids = .5 * (zz[..., 1:] + zz[..., :-1])
+                    upper, lower = torch.cat([mids, zz[..., -1:]], -1), torch.cat([zz[..., :1], mids], -1)
+                    if pytest:
+                        np.random.seed(0)
+                        t_rand = torch.Tensor(np.random.rand(R, S)).to(dev)
+                    else:
+                        t_rand = torch.rand(R, S, device=dev)
+                    z, z_stride = (lower + (upper - lower) * t_rand).contiguous(), S
+
+                def one_pass(net, zv, zs, n_s, which):
+                    h, fold = self._hip(net), folded[id(net)]
+                    sigma = torch.empty(R, n_s, dtype=torch.float32, device=dev)
+                    if occupancy is None:
+                        rays_per = max(1, int(self.netchunk) // n_s)
+                        pts = torch.empty(min(R, rays_per) * n_s, 3, dtype=torch.float32, device=dev)
+                        for i in range(0, R, rays_per):
+                            j = min(R, i + rays_per)
+                            m = (j - i) * n_s
+                            lib.check(L.mofa_ray_points(lib.ptr(ro[i:j]), lib.ptr(rd[i:j]), lib.ptr(zv[i:j] if zs else zv), zs, j - i, n_s,
+                                                        lib.ptr(pts[:m]), st), "mofa_ray_points")
+                            h.density_points(pts[:m], sigma[i:j].reshape(-1), fold)
+                    else:      # classify, compact (one host read: n_kept), density of the kept points, scatter (writes every element)
+                        from .occupancy import CulledPass
+                        cp = CulledPass(occupancy, ro, rd, zv, zs, n_s)
+                        stats = self.occupancy_stats.setdefault(which, {"samples": 0, "kept": 0})
+                        stats["samples"] += cp.n_samples
+                        stats["kept"] += cp.n_kept
+                        kept = None
+                        if cp.n_kept:
+                            pts, _, _ = cp.gather(vd)
+                            kept = torch.empty(cp.n_kept, dtype=torch.float32, device=dev)
+                            per = max(1, int(self.netchunk))
+                            for i in range(0, cp.n_kept, per):
+                                h.density_points(pts[i:i + per], kept[i:i + per], fold)
+                        cp.scatter_sigma(kept, sigma)
+                    o = {k: torch.empty(R, *shp, dtype=torch.float32, device=dev)
+                         for k, shp in (("disp", ()), ("acc", ()), ("depth", ()), ("weights", (n_s,)))}
+                    lib.check(L.mofa_composite_sigma(lib.ptr(sigma), lib.ptr(zv), zs, lib.ptr(rd), None, R, n_s, lib.ptr(o["disp"]),
+                                                     lib.ptr(o["acc"]), lib.ptr(o["depth"]), lib.ptr(o["weights"]), st), "mofa_composite_sigma")
+                    return o
+
+                c = one_pass(network_fn, z, z_stride, S, "coarse")
+                ret = {"depth": c["depth"], "disp": c["disp"], "acc": c["acc"]}
+                z_last, w_last = (z if z_stride else z[None, :].expand(R, S)), c["weights"]
+                if fine_pass:
+                    if perturb == 0.:
+                        u, u_stride = self._const_row(("u", Ni), lambda: torch.linspace(0., 1., steps=Ni), dev), 0
+                    elif pytest:
+                        np.random.seed(0)
+                        u, u_stride = torch.Tensor(np.random.rand(R, Ni)).to(dev).contiguous(), Ni
+                    else:
+                        u, u_stride = torch.rand(R, Ni, device=dev), Ni
+                    z_samples = torch.empty(R, Ni, dtype=torch.float32, device=dev)
+                    z_fine = torch.empty(R, S + Ni, dtype=torch.float32, device=dev)
+                    z_std = torch.empty(R, dtype=torch.float32, device=dev)
+                    lib.check(L.mofa_sample_pdf_merge(lib.ptr(z), z_stride, lib.ptr(c["weights"]), lib.ptr(u), u_stride, R, S, Ni,
+                                                      lib.ptr(z_samples), lib.ptr(z_fine), lib.ptr(z_std), st), "mofa_sample_pdf_merge")
+                    f = one_pass(fine, z_fine, S + Ni, S + Ni, "fine")
+                    ret = {"depth": f["depth"], "disp": f["disp"], "acc": f["acc"], "depth0": c["depth"], "disp0": c["disp"],
+                           "acc0": c["acc"], "z_std": z_std}
+                    z_last, w_last = z_fine, f["weights"]
+                if retweights:
+                    ret["weights"], ret["z_vals"] = w_last, z_last
+                for k, v in ret.items():
+                    out.setdefault(k, []).append(v)
+            full = {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in out.items()}
+            full = {k: torch.reshape(v, list(sh[:-1]) + list(v.shape[1:])) for k, v in full.items()}
+        return [full.pop("depth"), full.pop("disp"), full.pop("acc"), full]
+
     def build_occupancy(self, networks, *, bounds, resolution, threshold, shapeCodes, expType=20, expCodes=None, dilate=1, netchunk=None):
         """Occupancy grid for ``render_rays(..., occupancy=...)``: the density of each of ``networks`` (one network or a sequence,
         normally coarse and fine) from :meth:`query_density` on the lattice ``bounds`` x ``resolution``; a cell is occupied iff one of
