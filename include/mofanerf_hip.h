@@ -460,6 +460,23 @@ int mofa_ray_points(const float* rays_o, const float* rays_d, const float* z, in
 int mofa_composite_sigma(const float* sigma, const float* z, int64_t z_row_stride, const float* rays_d, const float* noise,
                          int64_t n_rays, int32_t S, float* disp, float* acc, float* depth, float* weights, void* stream);
 
+/* Median termination depth of a ray from its compositing weights [n_rays,S]: index[r] (int32) = the least i whose inclusive prefix sum
+ * C_i = w_0 + ... + w_i reaches `threshold` (C_i >= threshold), depth_med[r] = z[r][index[r]]; when no C_i reaches it (a ray through
+ * empty space; a NaN weight in front of the crossing) index = -1 and depth_med = z[r][S-1].  Every C_i is an fp32 sum of exactly
+ * w_0..w_i (one wavefront per ray: in-lane running sums under a wavefront scan), so it lies within (S-1) 2^-24 sum|w| of the exact sum.
+ * z as above (stride S or 0); S >= 1, fewer than 2^31 samples; threshold finite and > 0. */
+int mofa_depth_median(const float* weights, const float* z, int64_t z_row_stride, int64_t n_rays, int32_t S, float threshold,
+                      float* depth_med, int32_t* index, void* stream);
+
+/* Screen-space normals of a point map: points [H,W,3], acc [H,W], rays_d [H,W,3] -> normals [H,W,3], valid [H,W] (uint8).  A pixel is
+ * usable iff acc >= acc_min (NaN is not).  Along each image axis the difference is central (P[+1] - P[-1]) when both neighbours exist and
+ * are usable, else forward (P[+1] - P), else backward (P - P[-1]), else the pixel is invalid.  n = du x dv (du along columns, dv along
+ * rows; products and subtraction rounded separately), len = sqrt((nx nx + ny ny) + nz nz) correctly rounded, invalid unless len > 0, n / len, negated
+ * where (nx dx + ny dy) + nz dz > 0 so that normals face the camera.  Every element is written: unusable or invalid pixels get (0,0,0)
+ * and valid = 0 (a 1 x W or H x 1 map comes out all invalid).  Fewer than 2^31 pixels; acc_min finite. */
+int mofa_point_normals(const float* points, const float* acc, const float* rays_d, int32_t H, int32_t W, float acc_min, float* normals,
+                       uint8_t* valid, void* stream);
+
 /* sample_pdf on (z_mid, weights[1:-1]) + sort(cat(z, z_samples)) + std(z_samples)
  * (render_class.py:324-328,345; tools/run_nerf_helpers.py:203-247).  u: [n_rays,Ni] (stride Ni) or a
  * shared row (stride 0) — linspace(0,1,Ni) for det. */

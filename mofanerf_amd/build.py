@@ -12,8 +12,10 @@ OUT = os.path.join(HERE, "libmofanerf_hip.so")
 SOURCES = ["mofa_mlp.hip", "mofa_rays.hip", "mofa_bwd.hip", "mofa_net.hip", "mofa_mesh.hip", "mofa_occ.hip"]
 # -fvisibility=hidden: the library exports exactly the C ABI of include/mofanerf_hip.h (declared under a visibility pragma there);
 # the mofa_internal_* hand-offs between the translation units stay out of the dynamic symbol table
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fvisibility=hidden", "-Wall",
-         "-Wno-unused-function"]
+# -fhip-fp32-correctly-rounded-divide-sqrt (the compiler's default, pinned here): k_point_normals' sqrtf and every fp32 division are the
+# correctly rounded ones the bit-for-bit tests restate on the host
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
+         "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 LINK_FLAGS = ["-Wl,--version-script=" + os.path.join(CSRC, "exports.map")]
 
 

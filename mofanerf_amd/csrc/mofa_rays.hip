@@ -394,6 +394,127 @@ __global__ __launch_bounds__(256) void k_ray_points(const float* __restrict__ ra
     for (int a = 0; a < 3; ++a) pts[e * 3 + a] = __fadd_rn(rays_o[r * 3 + a], __fmul_rn(rays_d[r * 3 + a], zv));
 }
 
+// ---- median termination depth: the first sample at which the accumulated weight reaches a threshold ---------------------------------
+// One wavefront per ray, k_composite_sigma's lane-to-sample assignment (lane l owns samples [l*SPL, l*SPL+SPL)).  The inclusive prefix
+// sum C_i = w_0 + ... + w_i is formed as (sum of the lanes in front, a 6-step wavefront scan of the lanes' totals) + (the lane's own
+// running sum): every C_i is an fp32 sum of exactly w_0..w_i (slots past S add an exact 0), so |C_i - exact| <= (S-1) 2^-24 sum|w|.
+// index = the least i with C_i >= threshold (a wavefront minimum over each lane's first hit), -1 if there is none; a NaN weight makes
+// every later C_i NaN, which compares false.  depth_med = z[index], z[S-1] for -1.
+__device__ __forceinline__ int wave_min_i(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+constexpr int kNoIndex = 0x7fffffff;
+
+// the least sample index of this pass whose prefix sum reaches the threshold (kNoIndex: none), the same value in every lane;
+// `carry` = the sum of the passes in front on entry, of the passes up to and including this one on return
+template <int SPL>
+__device__ __forceinline__ int median_pass(const float* __restrict__ wr, int base, int S, float threshold, int lane, float& carry) {
+    float run[SPL];
+    const int s0 = base + lane * SPL;
+    float tot = 0.f;
+#pragma unroll
+    for (int t = 0; t < SPL; ++t) {
+        const float w = (s0 + t < S) ? wr[s0 + t] : 0.f;
+        tot = t == 0 ? w : tot + w;
+        run[t] = tot;
+    }
+    float incl = tot;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl = incl + up;
+    }
+    float front = __shfl_up(incl, 1, 64);
+    front = lane == 0 ? carry : carry + front;
+    carry = carry + __shfl(incl, 63, 64);
+    int hit = kNoIndex;
+#pragma unroll
+    for (int t = SPL - 1; t >= 0; --t)
+        if (s0 + t < S && front + run[t] >= threshold) hit = s0 + t;
+    return wave_min_i(hit);
+}
+
+template <int SPL>
+__global__ __launch_bounds__(256) void k_depth_median(const float* __restrict__ weights, const float* __restrict__ z,
+                                                      long long z_row_stride, long long n_rays, int S, float threshold,
+                                                      float* __restrict__ depth_med, int* __restrict__ index) {
+    const int lane = threadIdx.x & 63;
+    const long long ray = (long long)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    float carry = 0.f;
+    const int hit = median_pass<SPL>(weights + ray * (long long)S, 0, S, threshold, lane, carry);
+    if (lane == 0) {
+        const float* zr = z + ray * z_row_stride;
+        index[ray] = hit == kNoIndex ? -1 : hit;
+        depth_med[ray] = zr[hit == kNoIndex ? S - 1 : hit];
+    }
+}
+
+// more than 256 samples: passes of 256 samples (lane l owns samples [256 p + 4 l, +4) of pass p), the sum of the passes in front carried
+__global__ __launch_bounds__(256) void k_depth_median_long(const float* __restrict__ weights, const float* __restrict__ z,
+                                                           long long z_row_stride, long long n_rays, int S, float threshold,
+                                                           float* __restrict__ depth_med, int* __restrict__ index) {
+    const int lane = threadIdx.x & 63;
+    const long long ray = (long long)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    float carry = 0.f;
+    int hit = kNoIndex;
+    for (int base = 0; base < S && hit == kNoIndex; base += 256)      // (hit is the same in every lane: the wavefront leaves together)
+        hit = median_pass<4>(weights + ray * (long long)S, base, S, threshold, lane, carry);
+    if (lane == 0) {
+        const float* zr = z + ray * z_row_stride;
+        index[ray] = hit == kNoIndex ? -1 : hit;
+        depth_med[ray] = zr[hit == kNoIndex ? S - 1 : hit];
+    }
+}
+
+// ---- screen-space normals of a point map ---------------------------------------------------------------------------------------------
+// One thread per pixel of an H x W map.  A pixel is usable iff acc >= acc_min (NaN is not).  Along each image axis the difference is
+// central (P[+1] - P[-1]) when both neighbours exist and are usable, else forward (P[+1] - P), else backward (P - P[-1]), else the pixel
+// is invalid.  n = du x dv (two rounded products and one rounded subtraction per component), divided by its rounded length, turned to
+// face the camera (n . d <= 0); the square root and the divisions are the correctly rounded ones.  Every output element is written: invalid pixels get (0,0,0) and valid = 0.
+__device__ __forceinline__ bool axis_difference(const float* __restrict__ P, const float* __restrict__ acc, float acc_min, long long p,
+                                                long long step, bool has_prev, bool has_next, float out[3]) {
+    const bool prev = has_prev && acc[p - step] >= acc_min, next = has_next && acc[p + step] >= acc_min;
+    if (!prev && !next) return false;
+    const long long a = next ? p + step : p, b = prev && next ? p - step : (next ? p : p - step);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = __fsub_rn(P[a * 3 + k], P[b * 3 + k]);
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_point_normals(const float* __restrict__ points, const float* __restrict__ acc,
+                                                       const float* __restrict__ rays_d, int H, int W, float acc_min,
+                                                       float* __restrict__ normals, unsigned char* __restrict__ valid) {
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (long long)H * W) return;
+    const int r = (int)(p / W), c = (int)(p - (long long)r * W);
+    float du[3], dv[3], n[3] = {0.f, 0.f, 0.f};
+    bool ok = acc[p] >= acc_min;
+    ok = ok && axis_difference(points, acc, acc_min, p, 1, c > 0, c + 1 < W, du);
+    ok = ok && axis_difference(points, acc, acc_min, p, W, r > 0, r + 1 < H, dv);
+    if (ok) {
+        const float nx = __fsub_rn(__fmul_rn(du[1], dv[2]), __fmul_rn(du[2], dv[1]));
+        const float ny = __fsub_rn(__fmul_rn(du[2], dv[0]), __fmul_rn(du[0], dv[2]));
+        const float nz = __fsub_rn(__fmul_rn(du[0], dv[1]), __fmul_rn(du[1], dv[0]));
+        // sqrtf, not __fsqrt_rn: the latter is the hardware's approximate square root here, sqrtf the correctly rounded one a host restates
+        const float len = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(nx, nx), __fmul_rn(ny, ny)), __fmul_rn(nz, nz)));
+        ok = len > 0.f;
+        if (ok) {
+            n[0] = __fdiv_rn(nx, len), n[1] = __fdiv_rn(ny, len), n[2] = __fdiv_rn(nz, len);
+            const float s = __fadd_rn(__fadd_rn(__fmul_rn(n[0], rays_d[p * 3]), __fmul_rn(n[1], rays_d[p * 3 + 1])),
+                                      __fmul_rn(n[2], rays_d[p * 3 + 2]));
+            if (s > 0.f) n[0] = -n[0], n[1] = -n[1], n[2] = -n[2];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) normals[p * 3 + k] = n[k];
+    valid[p] = ok ? 1 : 0;
+}
+
 // ---- sample_pdf + sort(cat) + std (tools/run_nerf_helpers.py:203-247; render_class.py:324-328,345) ----
 // One wavefront per ray.  B = S-1 bin edges z_mid, B-1 = S-2 interior weights.
 // cdf follows the CPU reference: cumsum accumulates in double and rounds every prefix to float.
@@ -621,6 +742,40 @@ int mofa_ray_points(const float* rays_o, const float* rays_d, const float* z, in
     hipLaunchKernelGGL(k_ray_points, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, z,
                        (long long)z_row_stride, n, (int)S, pts);
     return check_launch("k_ray_points");
+}
+
+int mofa_depth_median(const float* weights, const float* z, int64_t z_row_stride, int64_t n_rays, int32_t S, float threshold,
+                      float* depth_med, int32_t* index, void* stream) {
+    MOFA_REQUIRE(weights && z && depth_med && index, "depth_median: null pointer");
+    MOFA_REQUIRE(n_rays >= 1 && S >= 1 && n_rays < (1ll << 31) && n_rays * (int64_t)S < (1ll << 31),
+                 "depth_median: %lld rays x %d samples (want at least one and fewer than 2^31 samples)", (long long)n_rays, (int)S);
+    MOFA_REQUIRE(z_row_stride == 0 || z_row_stride == S, "depth_median: z_row_stride = %lld with S = %d (want 0 or S)",
+                 (long long)z_row_stride, (int)S);
+    MOFA_REQUIRE(threshold > 0.f && threshold <= 3.402823466e38f, "depth_median: threshold = %g (want finite and > 0)", (double)threshold);
+    const dim3 grid(blocks_for(n_rays, kWavesPerBlock)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define MOFA_DEPTH_MEDIAN(SPL)                                                                                                  \
+    hipLaunchKernelGGL((k_depth_median<SPL>), grid, block, 0, st, weights, z, (long long)z_row_stride, (long long)n_rays, (int)S, \
+                       threshold, depth_med, (int*)index)
+    if (S <= 64) MOFA_DEPTH_MEDIAN(1);
+    else if (S <= 128) MOFA_DEPTH_MEDIAN(2);
+    else if (S <= 256) MOFA_DEPTH_MEDIAN(4);
+    else
+        hipLaunchKernelGGL(k_depth_median_long, grid, block, 0, st, weights, z, (long long)z_row_stride, (long long)n_rays, (int)S,
+                           threshold, depth_med, (int*)index);
+#undef MOFA_DEPTH_MEDIAN
+    return check_launch("k_depth_median");
+}
+
+int mofa_point_normals(const float* points, const float* acc, const float* rays_d, int32_t H, int32_t W, float acc_min, float* normals,
+                       uint8_t* valid, void* stream) {
+    MOFA_REQUIRE(points && acc && rays_d && normals && valid, "point_normals: null pointer");
+    MOFA_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W < (1ll << 31), "point_normals: a %d x %d map (want at least 1 x 1 and fewer than 2^31 pixels)",
+                 (int)H, (int)W);
+    MOFA_REQUIRE(acc_min >= -3.402823466e38f && acc_min <= 3.402823466e38f, "point_normals: acc_min = %g (want a finite value)", (double)acc_min);
+    hipLaunchKernelGGL(k_point_normals, dim3(blocks_for((long long)H * W, 256)), dim3(256), 0, (hipStream_t)stream, points, acc, rays_d,
+                       (int)H, (int)W, acc_min, normals, (unsigned char*)valid);
+    return check_launch("k_point_normals");
 }
 
 int mofa_sample_pdf_merge(const float* z, int64_t z_row_stride, const float* weights, const float* u,

@@ -121,6 +121,8 @@ SIGNATURES = {
     "mofa_composite_forward": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _i64, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp]),
     "mofa_ray_points": (C.c_int, [_fp, _fp, _fp, _i64, _i64, _i32, _fp, _fp]),
     "mofa_composite_sigma": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _i64, _i32, _fp, _fp, _fp, _fp, _fp]),
+    "mofa_depth_median": (C.c_int, [_fp, _fp, _i64, _i64, _i32, C.c_float, _fp, _fp, _fp]),
+    "mofa_point_normals": (C.c_int, [_fp, _fp, _fp, _i32, _i32, C.c_float, _fp, _fp, _fp]),
     "mofa_sample_pdf_merge": (C.c_int, [_fp, _i64, _fp, _fp, _i64, _i64, _i32, _i32, _fp, _fp, _fp, _fp]),
     "mofa_sample_pdf": (C.c_int, [_fp, _i64, _fp, _fp, _i64, _i64, _i32, _i32, _fp, _fp]),
 }

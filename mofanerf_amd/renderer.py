@@ -742,7 +742,8 @@ class Renderer(torch.nn.Module):
     _GEOMETRY_IGNORES = ("white_bkgd", "use_viewdirs", "retraw", "network_query_fn", "verbose")     # none of them changes geometry
 
     def render_geometry(self, H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., shapeCodes=None, expType=20,
-                        expCodes=None, c2w_staticcam=None, occupancy=None, retweights=False, **render_kwargs):
+                        expCodes=None, c2w_staticcam=None, occupancy=None, retweights=False, median=False, points=False, normals=False,
+                        surface="median", acc_min=0.5, median_threshold=0.5, **render_kwargs):
         """Geometry-only render: ``depth, disp, acc, extras`` of a frame from the density alone — no texture stack, no view layer, no rgb
         head, one float per sample instead of four.  Takes the ``render_kwargs_test`` dictionary the scripts hand to
         :meth:`render_fitting` (``network_fn``, ``network_fine``, ``N_samples``, ``N_importance``, ``perturb``, ``lindisp``, ``pytest``
@@ -758,7 +759,37 @@ class Renderer(torch.nn.Module):
         (``self.occupancy_stats`` is filled the same way).  ``extras``: ``depth0``, ``disp0``, ``acc0``, ``z_std`` when a fine pass ran;
         with ``retweights=True`` also ``weights`` and ``z_vals`` of the final pass.  Inference only: runs under ``torch.no_grad()`` on
         detached inputs.  No host synchronisation apart from the culled passes' kept counts; ``frame_check`` / ``check_launches`` work
-        afterwards as for :meth:`render`."""
+        afterwards as for :meth:`render`.
+
+        Surface buffers (all off by default; with all of them off the method launches exactly what it launches without them), formed
+        on the final pass — the fine one if it ran, otherwise the coarse one — and returned in ``extras``:
+
+        * ``median=True``: ``depth_median`` and ``median_index`` (int32) from ``mofa_depth_median`` on the pass's compositing weights,
+          per chunk of rays: the first sample whose accumulated weight reaches ``median_threshold``; rays on which it never does get
+          index -1 and the last sample's depth.
+        * ``points=True``: ``points [...,3] = o + d * depth_surface`` (``mofa_ray_points``, one sample per ray), where
+          ``depth_surface`` is ``depth_median`` for ``surface="median"`` and the expected depth ``depth`` for ``surface="expected"``.
+        * ``normals=True``: ``normals [H,W,3]`` and ``normals_valid [H,W]`` (uint8) from ``mofa_point_normals`` on the whole frame's
+          points, ``acc`` and ray directions: screen-space differences between pixels with ``acc >= acc_min``, facing the camera,
+          zero where invalid.  Needs a 2-D grid of rays: ``c2w``, or ``rays`` shaped ``[2,H,W,3]``.
+
+        ``normals`` implies ``points``, and ``points`` with ``surface="median"`` implies ``median``; what was implied is returned as
+        well.  ``points`` and ``normals`` are refused with ``ndc=True``: the sampler's rays are NDC rays then, and neither a point on
+        them nor a difference of such points is a position or a direction in the scene."""
+        if surface not in ("median", "expected"):
+            raise lib.MofaError(f"render_geometry: surface = {surface!r} (want 'median' or 'expected')")
+        if not (np.isfinite(_scalar(median_threshold)) and _scalar(median_threshold) > 0.):
+            raise lib.MofaError(f"render_geometry: median_threshold = {_scalar(median_threshold)} (want a finite value > 0)")
+        if not np.isfinite(_scalar(acc_min)):
+            raise lib.MofaError(f"render_geometry: acc_min = {_scalar(acc_min)} (want a finite value)")
+        want_points = bool(points or normals)
+        want_median = bool(median or (want_points and surface == "median"))
+        if normals and c2w is None and (rays is None or rays[1].dim() != 3):
+            raise lib.MofaError("render_geometry: normals=True needs a 2-D grid of rays (c2w, or rays shaped [2,H,W,3]); got a flat list of rays "
+                                f"{[2] + list(rays[1].shape) if rays is not None else None}")
+        if want_points and ndc:
+            raise lib.MofaError("render_geometry: points / normals with ndc=True: the sampler's rays are NDC rays, a point on them is no scene "
+                                "position (render with ndc=False)")
         for k in render_kwargs:
             if k not in self._GEOMETRY_READS and k not in self._GEOMETRY_IGNORES:
                 raise lib.MofaError(f"render_geometry: unknown argument {k!r} (reads {', '.join(self._GEOMETRY_READS)}; ignores "
@@ -860,6 +891,7 @@ class Renderer(torch.nn.Module):
                 c = one_pass(network_fn, z, z_stride, S, "coarse")
                 ret = {"depth": c["depth"], "disp": c["disp"], "acc": c["acc"]}
                 z_last, w_last = (z if z_stride else z[None, :].expand(R, S)), c["weights"]
+                z_med, zs_med = z, z_stride
                 if fine_pass:
                     if perturb == 0.:
                         u, u_stride = self._const_row(("u", Ni), lambda: torch.linspace(0., 1., steps=Ni), dev), 0
@@ -877,13 +909,112 @@ class Renderer(torch.nn.Module):
                     ret = {"depth": f["depth"], "disp": f["disp"], "acc": f["acc"], "depth0": c["depth"], "disp0": c["disp"],
                            "acc0": c["acc"], "z_std": z_std}
                     z_last, w_last = z_fine, f["weights"]
+                    z_med, zs_med = z_fine, S + Ni
                 if retweights:
                     ret["weights"], ret["z_vals"] = w_last, z_last
+                if want_median:      # on the final pass's compositing weights, as the kernel wrote them
+                    ret["depth_median"] = torch.empty(R, dtype=torch.float32, device=dev)
+                    ret["median_index"] = torch.empty(R, dtype=torch.int32, device=dev)
+                    lib.check(L.mofa_depth_median(lib.ptr(w_last), lib.ptr(z_med), zs_med, R, int(w_last.shape[1]), _scalar(median_threshold),
+                                                  lib.ptr(ret["depth_median"]), ret["median_index"].data_ptr(), st), "mofa_depth_median")
                 for k, v in ret.items():
                     out.setdefault(k, []).append(v)
             full = {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in out.items()}
+            if want_points:          # one launch each on the whole frame: a normal reads its pixel's neighbours, which a chunk of rays cuts apart
+                surf = (full["depth_median"] if surface == "median" else full["depth"]).contiguous()
+                full["points"] = torch.empty(n_rays, 3, dtype=torch.float32, device=dev)
+                lib.check(L.mofa_ray_points(lib.ptr(rays_o), lib.ptr(rays_d), lib.ptr(surf), 1, n_rays, 1, lib.ptr(full["points"]), st),
+                          "mofa_ray_points")
+            if normals:
+                full["normals"] = torch.empty(n_rays, 3, dtype=torch.float32, device=dev)
+                full["normals_valid"] = torch.empty(n_rays, dtype=torch.uint8, device=dev)
+                lib.check(L.mofa_point_normals(lib.ptr(full["points"]), lib.ptr(full["acc"].contiguous()), lib.ptr(rays_d), int(sh[0]), int(sh[1]),
+                                               _scalar(acc_min), lib.ptr(full["normals"]), full["normals_valid"].data_ptr(), st),
+                          "mofa_point_normals")
             full = {k: torch.reshape(v, list(sh[:-1]) + list(v.shape[1:])) for k, v in full.items()}
         return [full.pop("depth"), full.pop("disp"), full.pop("acc"), full]
+
+    _PATH_GEOMETRY_OPTIONS = ("surface", "acc_min", "median_threshold", "occupancy")
+
+    def render_path_geometry(self, render_poses, hwf, K, chunk, render_kwargs, expType=None, expCodes=None, shapeCodes=None, savedir=None,
+                             render_factor=0, name=None, near=None, far=None, **surface):
+        """The geometry twin of :meth:`render_path`: one :meth:`render_geometry` frame per pose with its surface buffers on (normals,
+        points and — for ``surface="median"`` — the median depth).  ``surface`` options: ``surface``, ``acc_min``, ``median_threshold``,
+        ``occupancy``.  ``near`` / ``far`` (scalars) default to the ones in ``render_kwargs``, ``ndc`` to ``render_kwargs["ndc"]`` and, without one, to
+        ``False`` (points and normals are refused on NDC rays).  ``shapeCodes`` / ``expCodes`` with one row
+        per pose are taken row by row, otherwise shared; ``expType`` likewise (default 20).
+
+        With ``savedir`` three 8-bit PNGs per pose go through the ``PngSink`` with the frame's ``frame_check``: ``<stem>_normals.png``
+        (``valid * (n + 1) / 2``: invalid pixels are black), ``<stem>_mask.png`` (the pixels with ``acc >= acc_min``) and
+        ``<stem>_depth.png`` (``(depth_surface - near) / (far - near)`` in grey); ``stem`` is the pose's number, or ``name`` (followed by
+        the number when there are several poses).  A pose whose three files exist is skipped, so a bulk render can resume.  Returns a
+        dict of numpy arrays stacked over the rendered poses — ``depth``, ``disp``, ``acc``, ``depth_surface``, ``points``, ``normals``,
+        ``normals_valid`` and ``depth_median`` / ``median_index`` when they were formed — with ``rendered`` and ``skipped``, the lists
+        of pose numbers."""
+        for k in surface:
+            if k not in self._PATH_GEOMETRY_OPTIONS:
+                raise lib.MofaError(f"render_path_geometry: unknown argument {k!r} (surface options: {', '.join(self._PATH_GEOMETRY_OPTIONS)})")
+        height, width, focal = hwf
+        if render_factor:                                   # render downsampled
+            height, width, focal = height // render_factor, width // render_factor, focal / render_factor
+        kw = dict(render_kwargs)
+        kw_near, kw_far = kw.pop("near", None), kw.pop("far", None)
+        ndc = kw.pop("ndc", False)
+        near, far = (kw_near if near is None else near), (kw_far if far is None else far)
+        if near is None or far is None:
+            raise lib.MofaError("render_path_geometry: near and far are required (as arguments or in render_kwargs)")
+        near, far = _scalar(near), _scalar(far)
+        if not far > near:
+            raise lib.MofaError(f"render_path_geometry: near = {near}, far = {far} (want far > near)")
+        n_poses = len(render_poses)
+        which = surface.get("surface", "median")
+        acc_min = surface.get("acc_min", 0.5)
+
+        def row(v, i):
+            return v[i].reshape(1, -1) if torch.is_tensor(v) and v.dim() == 2 and v.shape[0] == n_poses and n_poses > 1 else v
+
+        def stem(i):
+            if name is None:
+                return "{:03d}".format(i)
+            return str(name) if n_poses == 1 else "{}_{:03d}".format(name, i)
+
+        def files(i):
+            return [os.path.join(savedir, stem(i) + tail) for tail in ("_normals.png", "_mask.png", "_depth.png")]
+
+        from .io import PngSink
+        frames: Dict[str, list] = {}
+        rendered, skipped = [], []
+        shared = self.png_sink
+        sink = shared if shared is not None else PngSink()
+        try:
+            for i, pose in enumerate(render_poses):
+                paths = files(i) if savedir is not None else None
+                if paths is not None and all(os.path.exists(f) for f in paths):
+                    skipped.append(i)                       # bulk renders resume by skipping finished poses
+                    continue
+                et = 20 if expType is None else (expType[i] if hasattr(expType, "__len__") else expType)
+                depth, disp, acc, ex = self.render_geometry(height, width, K, chunk=chunk, c2w=pose[:3, :4], ndc=ndc, near=near, far=far,
+                                                            shapeCodes=row(shapeCodes, i), expType=et, expCodes=row(expCodes, i),
+                                                            normals=True, **surface, **kw)
+                surf = ex["depth_median"] if which == "median" else depth
+                if paths is not None:
+                    valid = ex["normals_valid"].to(torch.float32)[..., None]
+                    grey = lambda t: t[..., None].expand(*t.shape, 3)
+                    span = torch.full_like(surf, far - near)          # a tensor divisor: an elementwise, correctly rounded division
+                    check = self.frame_check()                       # one snapshot of this frame's verdicts for its three files
+                    for f, img in zip(paths, (valid * ((ex["normals"] + 1.) / 2.), grey((acc >= _scalar(acc_min)).to(torch.float32)),
+                                              grey((surf - near) / span))):
+                        sink.submit(f, img, check=check)
+                rendered.append(i)
+                for k, v in dict(ex, depth=depth, disp=disp, acc=acc, depth_surface=surf).items():
+                    frames.setdefault(k, []).append(v.detach())
+        finally:
+            if shared is None:
+                sink.close()
+        out = {k: torch.stack(v, 0).cpu().numpy() for k, v in frames.items()}
+        out["rendered"], out["skipped"] = rendered, skipped
+        self.check_launches(block=True)
+        return out
 
     def build_occupancy(self, networks, *, bounds, resolution, threshold, shapeCodes, expType=20, expCodes=None, dilate=1, netchunk=None):
         """Occupancy grid for ``render_rays(..., occupancy=...)``: the density of each of ``networks`` (one network or a sequence,

@@ -6,6 +6,11 @@ whether the outputs the two renders share (disp, acc, disp0, acc0, z_std) are bi
 network's dense FLOPs from ``mofa_net_layer_dims``.  Writes ``depth.npy``, ``acc.npy``, ``disp.npy`` and ``mask.png`` (acc through
 ``mesh.to8b``) into ``--out``.
 
+``--surface median|expected`` adds a fourth arm, timed right after the geometry arm in the same process: the geometry render with its
+surface buffers on (``normals=True``: median depth, points, normals).  It writes ``normals.png`` (``valid * (n + 1) / 2``),
+``depth_median.npy`` and ``points.npy`` as well, and the line carries the arm's times, its ratio to the plain geometry arm, the share of
+pixels with a valid normal and whether the buffers both arms share are bit-identical.
+
 Networks come from a checkpoint (``--ckpt DIR`` or one ``.tar``) or from seeded synthetic weights (``--synthetic DC WC DF WF``); codes
 from ``--fit saving_Parameters.tar`` or ``synth.codes`` — the options of tools/render_culled.py.  Seeded weights say nothing about a
 trained face's live fraction: the gated full render's time depends on it, the other two arms do not.
@@ -61,6 +66,9 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=5, help="timed frames per arm (the median is reported)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default="geometry_out", help="directory for depth.npy, acc.npy, disp.npy and mask.png")
+    ap.add_argument("--surface", choices=("median", "expected"), help="also time and write the surface buffers (normals, points, median depth)")
+    ap.add_argument("--acc-min", type=float, default=0.5, help="--surface: a pixel takes part in the normals iff acc >= this")
+    ap.add_argument("--median-threshold", type=float, default=0.5, help="--surface: the accumulated weight the median depth is taken at")
     a = ap.parse_args(argv)
     dev = torch.device("cuda", torch.cuda.current_device())
     render, kw, bm, uv, exp = load(a, dev)
@@ -71,6 +79,13 @@ def main(argv=None):
 
     def geometry():
         out = render.render_geometry(H, H, K, chunk=a.chunk, c2w=pose, shapeCodes=bm, expType=20, expCodes=exp, **kw)
+        render.check_launches(block=True)
+        torch.cuda.synchronize()
+        return out
+
+    def surface():
+        out = render.render_geometry(H, H, K, chunk=a.chunk, c2w=pose, shapeCodes=bm, expType=20, expCodes=exp, median=True, normals=True,
+                                     surface=a.surface, acc_min=a.acc_min, median_threshold=a.median_threshold, **kw)
         render.check_launches(block=True)
         torch.cuda.synchronize()
         return out
@@ -94,6 +109,8 @@ def main(argv=None):
 
     keep = os.environ.get("MOFA_GATE")
     t_geo, g = arm(geometry)
+    if a.surface:
+        t_surf, gs = arm(surface)
     os.environ["MOFA_GATE"] = "0"
     lib.reload_env()
     try:
@@ -117,12 +134,25 @@ def main(argv=None):
         np.save(os.path.join(a.out, name + ".npy"), arr)
     from mofanerf_amd.io import write_png
     write_png(os.path.join(a.out, "mask.png"), np.repeat(mesh.to8b(acc)[..., None], 3, -1))
+    extra = {}
+    if a.surface:
+        identical["surface_frame"] = (all(bool(torch.equal(bits(x), bits(y))) for x, y in zip(g[:3], gs[:3])) and
+                                      all(bool(torch.equal(bits(g[3][k]), bits(gs[3][k]))) for k in g[3]))
+        normals, valid = gs[3]["normals"].cpu().numpy(), gs[3]["normals_valid"].cpu().numpy()
+        np.save(os.path.join(a.out, "depth_median.npy"), gs[3]["depth_median"].cpu().numpy())
+        np.save(os.path.join(a.out, "points.npy"), gs[3]["points"].cpu().numpy())
+        write_png(os.path.join(a.out, "normals.png"), mesh.to8b(valid[..., None] * (normals + 1.0) / 2.0))
+        extra = {"surface": a.surface, "acc_min": a.acc_min, "median_threshold": a.median_threshold, "geometry_surface": t_surf,
+                 "surface_over_geometry": round(t_surf["frame_ms_median"] / t_geo["frame_ms_median"], 4),
+                 "normals_valid_share": round(float(valid.mean()), 4), "usable_share": round(float((acc >= a.acc_min).mean()), 4),
+                 "median_found_share": round(float((gs[3]["median_index"] >= 0).float().mean()), 4)}
+        print(f"valid normals: {100 * extra['normals_valid_share']:.2f} % of {H * H} pixels", file=sys.stderr)
     print(json.dumps({"size": H, "samples": a.samples, "chunk": a.chunk, "netchunk": a.netchunk, "near": a.near, "far": a.far, "angle": a.angle,
                       "geometry": t_geo, "full_ungated": t_plain, "full_gated": t_gated,
                       "geometry_over_full_ungated": round(t_geo["frame_ms_median"] / t_plain["frame_ms_median"], 4),
                       "geometry_over_full_gated": round(t_geo["frame_ms_median"] / t_gated["frame_ms_median"], 4),
                       "bit_identical": identical, "fine_density_flop_share": round(geo_flops / all_flops, 4),
-                      "acc_mean": float(acc.mean()), "out": a.out}))
+                      "acc_mean": float(acc.mean()), "out": a.out, **extra}))
     return 0 if all(identical.values()) else 1
 
 
