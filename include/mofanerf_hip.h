@@ -490,6 +490,40 @@ int mofa_sample_pdf_merge(const float* z, int64_t z_row_stride, const float* wei
 int mofa_sample_pdf(const float* bins, int64_t bins_row_stride, const float* weights, const float* u, int64_t u_row_stride,
                     int64_t n_rays, int32_t n_bins, int32_t Ni, float* samples, void* stream);
 
+/* ---- mesh rasteriser: depth, face index, barycentrics, attributes and flat normals of a triangle mesh ------------------------
+ * verts [n_verts,3] fp32 (world), faces [n_faces,3] int32, c2w [3,4] row-major (DEVICE, as mofa_get_rays takes it), pinhole fx, fy, cx, cy.
+ * The camera is the one of mofa_get_rays: pixel (i, j) (column, row) is sampled at the integer point (i, j), the camera looks along -z,
+ * and `depth` is the ray parameter of that pixel's ray — the quantity mofa_composite_sigma / mofa_depth_median give without NDC.
+ *   vertex    d = v - t, p_a = (d0 c[0][a] + d1 c[1][a]) + d2 c[2][a], zc = -p_2, u = cx + fx (p_0 / zc), v = cy - fy (p_1 / zc), every
+ *             operation rounded separately; valid iff zc >= znear, |u| <= 2^20 and |v| <= 2^20 (false for NaN); X = rint(256 u), Y = rint(256 v)
+ *   face      culled whole when a corner is invalid or an index lies outside [0, n_verts) (no near-plane clipping); degenerate when
+ *             A = (X1-X0)(Y2-Y0) - (Y1-Y0)(X2-X0) is 0; otherwise drawn, either winding
+ *   coverage  int64 edge functions at (256 i, 256 j): w0 = s E(1,2), w1 = s E(2,0), w2 = s E(0,1), s = sign(A),
+ *             E(p,q) = (Xq-Xp)(Py-Yp) - (Yq-Yp)(Px-Xp); covered iff all three >= 0 (a sample on a shared edge belongs to both faces)
+ *   depth     fp64, rounded once: l_k = w_k / |A|, q = (l0/z0 + l1/z1) + l2/z2, depth = (float)(1/q), b_k = (l_k/z_k)/q,
+ *             attr_c = (float)((b0 a0c + b1 a1c) + b2 a2c)
+ *   pixel     the least (depth bits << 32 | face) over the faces that cover it (64-bit atomicMin on a z-buffer in the workspace): the
+ *             nearest face, the lower index at equal depth bits — whatever the order of the atomics
+ *   normal    n = (v1-v0) x (v2-v0) in the operation order of mofa_point_normals, (0,0,0) unless its length is > 0, n / len, negated
+ *             where n . d > 0 for the pixel's ray direction d
+ * Call order per frame, on one stream: project, faces, resolve (any number of resolves).  No call synchronises the host. */
+size_t mofa_raster_workspace_bytes(int64_t n_verts, int64_t n_faces, int32_t H, int32_t W);   /* 0 when refused: H or W < 1, H W >= 2^31,
+                                                                                                 a negative count, n_verts or n_faces >= 2^31 */
+/* one lane per vertex: snapped screen position, camera depth and validity into the workspace.  znear finite and > 0. */
+int mofa_raster_project(const float* verts, int64_t n_verts, int64_t n_faces, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                        const float* c2w, float znear, void* workspace, void* stream);
+/* clears the z-buffer and rasterises.  A face whose clipped box of samples holds fewer than wave_min_pixels (>= 0) pixels is walked by
+ * one lane, the others one wavefront per face (0: every face by a wavefront; INT32_MAX: every face by a lane) — the same bits either way.
+ * counts [4] int64 (DEVICE): faces drawn, culled, degenerate, and drawn faces that took the wavefront path.  n_faces or n_verts = 0 is
+ * valid: an empty frame. */
+int mofa_raster_faces(const int32_t* faces, int64_t n_faces, int64_t n_verts, int32_t H, int32_t W, int32_t wave_min_pixels, void* workspace,
+                      int64_t* counts, void* stream);
+/* one lane per pixel: depth [H,W], face [H,W] (int32) and, where not NULL, bary [H,W,3], attr_out [H,W,C] (attrs [n_verts,C], C in 1 .. 16)
+ * and normal [H,W,3].  Every element is written; an uncovered pixel gets depth 0, face -1 and zeros. */
+int mofa_raster_resolve(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* attrs, int32_t C, int32_t H,
+                        int32_t W, float fx, float fy, float cx, float cy, const float* c2w, const void* workspace, float* depth, int32_t* face,
+                        float* bary, float* attr_out, float* normal, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

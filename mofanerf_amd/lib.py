@@ -125,6 +125,11 @@ SIGNATURES = {
     "mofa_point_normals": (C.c_int, [_fp, _fp, _fp, _i32, _i32, C.c_float, _fp, _fp, _fp]),
     "mofa_sample_pdf_merge": (C.c_int, [_fp, _i64, _fp, _fp, _i64, _i64, _i32, _i32, _fp, _fp, _fp, _fp]),
     "mofa_sample_pdf": (C.c_int, [_fp, _i64, _fp, _fp, _i64, _i64, _i32, _i32, _fp, _fp]),
+    "mofa_raster_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "mofa_raster_project": (C.c_int, [_fp, _i64, _i64, _i32, _i32, C.c_float, C.c_float, C.c_float, C.c_float, _fp, C.c_float, _fp, _fp]),
+    "mofa_raster_faces": (C.c_int, [_fp, _i64, _i64, _i32, _i32, _i32, _fp, _fp, _fp]),
+    "mofa_raster_resolve": (C.c_int, [_fp, _i64, _fp, _i64, _fp, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp, _fp, _fp,
+                                      _fp, _fp, _fp, _fp]),
 }
 
 _lib: Optional[C.CDLL] = None

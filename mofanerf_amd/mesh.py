@@ -1,6 +1,7 @@
 """Geometry export: the grid of a density query, the iso-surface of a density grid on the GPU (``mofa_iso_count`` / ``mofa_iso_emit``,
 marching tetrahedra on the Freudenthal split), the same mesh from a narrow band of bricks around the surface (``band_surface``,
-``mofa_band_*``) and a binary PLY writer / reader.
+``mofa_band_*``), a binary PLY writer / reader, and the way back from a mesh to a camera: a GPU z-buffer rasteriser (``rasterize``,
+``mofa_raster_*``) whose depth is comparable with ``Renderer.render_geometry``'s, and ``depth_agreement`` between the two.
 
 ``Renderer.query_density`` and ``Renderer.extract_mesh`` are the user-facing entry points; this module holds the pieces they share.
 The mesh is watertight and consistently oriented (normals toward lower density); vertices and faces come out in a fixed order with
@@ -210,6 +211,107 @@ def vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
     return torch.nn.functional.normalize(n, dim=-1)
 
 
+INT32_MAX = 2 ** 31 - 1
+# faces whose clipped box of samples holds at least this many pixels are walked one wavefront per face (mofa_raster_faces); the choice
+# changes no bit of the frame.  profiles/mesh_raster.md holds the sweep it comes from.
+WAVE_MIN_PIXELS = 64
+
+
+def _pose_tensor(c2w, dev) -> torch.Tensor:
+    pose = torch.as_tensor(np.asarray(c2w.detach().cpu() if torch.is_tensor(c2w) else c2w), dtype=torch.float32)[:3, :4]
+    return pose.contiguous().to(dev)
+
+
+def rasterize(verts: torch.Tensor, faces: torch.Tensor, H: int, W: int, K, c2w, attrs: Optional[torch.Tensor] = None, znear: float = 1e-3,
+              bary: bool = False, normals: bool = False, wave_min_pixels: Optional[int] = None) -> dict:
+    """Rasterise a triangle mesh (``verts [V,3] float32``, ``faces [F,3] int32``, on the GPU) from the pinhole camera ``K`` / ``c2w`` of
+    ``get_rays`` (``mofa_raster_project`` / ``_faces`` / ``_resolve``): pixel (i, j) is sampled at the integer point, and ``depth`` is the
+    ray parameter of that pixel's ray — the depth ``Renderer.render_geometry`` gives without NDC.  Returns a dict of GPU tensors:
+    ``depth [H,W]`` (0 where nothing is hit), ``face [H,W] int32`` (-1), ``mask [H,W] bool`` (``face >= 0``), ``counts [4] int64`` (faces
+    drawn, culled — a vertex nearer than ``znear``, outside the 2^20-pixel guard band or non-finite, or an index out of range; there is
+    no near-plane clipping —, degenerate after the snap to 1/256 pixel, and drawn faces that took the wavefront path; read it only if
+    wanted: nothing here synchronises) and, on request, ``bary [H,W,3]`` (perspective-correct), ``attr [H,W,C]`` (``attrs [V,C]``, C in
+    1 .. 16, interpolated) and ``normal [H,W,3]`` (the face's unit normal, turned to the camera).  Both windings are drawn; the nearest
+    face wins and the lower index among equal depths, so the same input gives the same bits every time."""
+    H, W = int(H), int(W)
+    lib.ptr(verts)
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise lib.MofaError(f"rasterize: want verts [V,3], got {tuple(verts.shape)}")
+    if not faces.is_cuda:
+        raise lib.MofaError("the HIP path needs tensors on the GPU (got CPU faces); there is no CPU fallback")
+    if faces.dtype != torch.int32 or not faces.is_contiguous() or faces.dim() != 2 or faces.shape[1] != 3:
+        raise lib.MofaError(f"rasterize: want contiguous int32 faces [F,3], got {faces.dtype} {tuple(faces.shape)}")
+    dev = verts.device
+    if faces.device != dev:
+        raise lib.MofaError(f"rasterize: verts on {dev}, faces on {faces.device}")
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    C_attr = 0
+    if attrs is not None:
+        lib.ptr(attrs)
+        if attrs.dim() != 2 or attrs.shape[0] != V or attrs.device != dev:
+            raise lib.MofaError(f"rasterize: want attrs [{V},C] on {dev}, got {tuple(attrs.shape)} on {attrs.device}")
+        C_attr = int(attrs.shape[1])
+        if not 1 <= C_attr <= 16:
+            raise lib.MofaError(f"rasterize: C = {C_attr} attributes per vertex (want 1 .. 16)")
+    znear = float(znear)
+    if not (np.isfinite(znear) and znear > 0):
+        raise lib.MofaError(f"rasterize: znear = {znear} (want finite and > 0)")
+    wmp = WAVE_MIN_PIXELS if wave_min_pixels is None else int(wave_min_pixels)
+    if not 0 <= wmp <= INT32_MAX:
+        raise lib.MofaError(f"rasterize: wave_min_pixels = {wave_min_pixels} (want 0 .. 2^31 - 1)")
+    L = lib.load()
+    nbytes = L.mofa_raster_workspace_bytes(V, F, H, W) if (abs(H) <= INT32_MAX and abs(W) <= INT32_MAX) else 0
+    if nbytes == 0:
+        raise lib.MofaError(f"rasterize: H = {H}, W = {W} with {V} vertices and {F} faces is refused (H, W >= 1, H W < 2^31)")
+    fx, fy, cx, cy = float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
+    with torch.cuda.device(dev):
+        pose = _pose_tensor(c2w, dev)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = {"depth": torch.empty(H, W, dtype=torch.float32, device=dev), "face": torch.empty(H, W, dtype=torch.int32, device=dev),
+               "counts": torch.empty(4, dtype=torch.int64, device=dev)}
+        if bary:
+            out["bary"] = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+        if attrs is not None:
+            out["attr"] = torch.empty(H, W, C_attr, dtype=torch.float32, device=dev)
+        if normals:
+            out["normal"] = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+        stream = lib.stream()
+        lib.check(L.mofa_raster_project(verts.data_ptr(), V, F, H, W, fx, fy, cx, cy, lib.ptr(pose), znear, ws.data_ptr(), stream),
+                  "mofa_raster_project")
+        lib.check(L.mofa_raster_faces(faces.data_ptr(), F, V, H, W, wmp, ws.data_ptr(), out["counts"].data_ptr(), stream), "mofa_raster_faces")
+        lib.check(L.mofa_raster_resolve(verts.data_ptr(), V, faces.data_ptr(), F, lib.ptr(attrs), max(C_attr, 1), H, W, fx, fy, cx, cy, lib.ptr(pose),
+                                        ws.data_ptr(), lib.ptr(out["depth"]), out["face"].data_ptr(), lib.ptr(out.get("bary")),
+                                        lib.ptr(out.get("attr")), lib.ptr(out.get("normal")), stream), "mofa_raster_resolve")
+    out["mask"] = out["face"] >= 0
+    return out
+
+
+def depth_agreement(depth_mesh: torch.Tensor, mask_mesh: torch.Tensor, depth_vol: torch.Tensor, acc: torch.Tensor, acc_min: float) -> dict:
+    """How well a rasterised mesh lies where the volume renders its surface, from one camera: ``depth_mesh`` / ``mask_mesh`` of
+    :func:`rasterize`, ``depth_vol`` / ``acc`` of ``Renderer.render_geometry`` (non-NDC; the median depth is the one to compare a surface
+    with).  The volume's mask is ``acc >= acc_min``.  Returns ``iou`` (of the two masks; 1.0 when both are empty), ``n_mesh``, ``n_vol``,
+    ``n_both`` (pixel counts of each mask and of their overlap) and ``median_abs`` / ``p95_abs`` of ``|depth_mesh - depth_vol|`` on the
+    overlap (NaN when it is empty).  Plain torch; reads the results back."""
+    m = mask_mesh.to(torch.bool)
+    v = acc >= float(acc_min)
+    both = m & v
+    n_mesh, n_vol, n_both = int(m.sum()), int(v.sum()), int(both.sum())
+    union = n_mesh + n_vol - n_both
+    out = {"iou": n_both / union if union else 1.0, "n_mesh": n_mesh, "n_vol": n_vol, "n_both": n_both,
+           "median_abs": float("nan"), "p95_abs": float("nan")}
+    if n_both:
+        d = (depth_mesh[both].to(torch.float64) - depth_vol[both].to(torch.float64)).abs().sort().values
+
+        def quantile(q):                                  # linear between the two nearest ranks (numpy's default), on any number of pixels
+            pos = q * (n_both - 1)
+            lo = int(pos)
+            hi = min(lo + 1, n_both - 1)
+            return float(d[lo] + (d[hi] - d[lo]) * (pos - lo))
+
+        out["median_abs"], out["p95_abs"] = quantile(0.5), quantile(0.95)
+    return out
+
+
 def to8b(x) -> np.ndarray:
     """The reference's quantisation (tools/run_nerf_helpers.py:12): ``(255 * clip(x, 0, 1))`` truncated to uint8."""
     return (255 * np.clip(np.asarray(x, dtype=np.float32), 0, 1)).astype(np.uint8)
@@ -278,4 +380,5 @@ def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
     return verts, np.ascontiguousarray(frec["i"]).astype(np.int32).reshape(-1, 3), colors
 
 
-__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "vertex_normals", "to8b", "write_ply", "read_ply")
+__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "vertex_normals", "rasterize", "depth_agreement", "to8b", "write_ply",
+                           "read_ply")

@@ -1016,6 +1016,84 @@ class Renderer(torch.nn.Module):
         self.check_launches(block=True)
         return out
 
+    def render_mesh(self, H, W, K, c2w, verts, faces, colors=None, znear=1e-3, ambient=0.3):
+        """A view of a triangle mesh — what :meth:`extract_mesh` returns — from the camera ``K`` / ``c2w`` of ``get_rays``, by the GPU
+        rasteriser (``mesh.rasterize``; no network runs).  Returns ``(rgb [H,W,3], depth [H,W], mask [H,W] bool, extras)``; ``depth`` is
+        the ray parameter of the pixel's ray, the depth :meth:`render_geometry` gives without NDC, and 0 where nothing is hit.  With
+        ``colors [V,3]`` (``extract_mesh(colors=True)``) ``rgb`` is the perspective-correct interpolation of the vertex colours; without,
+        a head-light shade of the flat face normal ``n`` (turned to the camera): ``ambient + (1 - ambient) max(0, -n . d / |d|)`` for
+        the pixel's ray direction ``d``, black where nothing is hit.  ``extras``: ``face`` (int32, -1 where nothing is hit), ``counts``
+        (device int64 [4]: faces drawn, culled, degenerate, on the wavefront path) and, for the shade, ``normal``."""
+        from . import mesh
+        from .rays import get_rays
+        if colors is not None:
+            if colors.dim() != 2 or colors.shape[-1] != 3:
+                raise lib.MofaError(f"render_mesh: want colors [V,3], got {tuple(colors.shape)}")
+            out = mesh.rasterize(verts, faces, H, W, K, c2w, attrs=colors, znear=znear)
+            rgb = out["attr"]
+            extras = {"face": out["face"], "counts": out["counts"]}
+        else:
+            ambient = _scalar(ambient)
+            if not 0. <= ambient <= 1.:
+                raise lib.MofaError(f"render_mesh: ambient = {ambient} (want 0 .. 1)")
+            out = mesh.rasterize(verts, faces, H, W, K, c2w, znear=znear, normals=True)
+            _, d = get_rays(H, W, K, c2w, device=verts.device)
+            view = d / d.norm(dim=-1, keepdim=True)
+            shade = ambient + (1. - ambient) * (-(out["normal"] * view).sum(-1)).clamp(min=0.)
+            rgb = (shade * out["mask"].to(torch.float32))[..., None].expand(H, W, 3).contiguous()
+            extras = {"face": out["face"], "counts": out["counts"], "normal": out["normal"]}
+        return rgb, out["depth"], out["mask"], extras
+
+    def render_path_mesh(self, render_poses, hwf, K, verts, faces, colors=None, savedir=None, znear=1e-3, ambient=0.3, near=None, far=None,
+                         name=None):
+        """One :meth:`render_mesh` frame per pose: a turntable of an exported mesh at the cost of a z-buffer.  With ``savedir`` two 8-bit
+        PNGs per pose go through the ``PngSink``: ``<stem>_mesh.png`` (``rgb``) and ``<stem>_mesh_depth.png`` (``(depth - near) / (far -
+        near)`` in grey, black where nothing is hit; ``near`` / ``far`` default to the least and greatest depth of the frame); ``stem`` as
+        in :meth:`render_path_geometry`.  A pose whose two files exist is skipped.  Returns a dict of numpy arrays stacked over the
+        rendered poses — ``rgb``, ``depth``, ``mask``, ``face`` — with ``rendered`` and ``skipped``, the lists of pose numbers."""
+        height, width, _ = hwf
+        height, width = int(height), int(width)
+        n_poses = len(render_poses)
+        if (near is None) != (far is None) or (near is not None and not _scalar(far) > _scalar(near)):
+            raise lib.MofaError(f"render_path_mesh: near = {near}, far = {far} (want both or neither, far > near)")
+
+        def stem(i):
+            if name is None:
+                return "{:03d}".format(i)
+            return str(name) if n_poses == 1 else "{}_{:03d}".format(name, i)
+
+        from .io import PngSink
+        frames: Dict[str, list] = {}
+        rendered, skipped = [], []
+        shared = self.png_sink
+        sink = shared if shared is not None else PngSink()
+        try:
+            for i, pose in enumerate(render_poses):
+                paths = [os.path.join(savedir, stem(i) + tail) for tail in ("_mesh.png", "_mesh_depth.png")] if savedir is not None else None
+                if paths is not None and all(os.path.exists(f) for f in paths):
+                    skipped.append(i)
+                    continue
+                rgb, depth, mask, ex = self.render_mesh(height, width, K, pose[:3, :4], verts, faces, colors=colors, znear=znear, ambient=ambient)
+                if paths is not None:
+                    if near is None:
+                        hit = depth[mask]
+                        lo, hi = (hit.min(), hit.max()) if hit.numel() else (depth.new_zeros(()), depth.new_ones(()))
+                        span = torch.where(hi > lo, hi - lo, torch.ones_like(hi))
+                    else:
+                        lo, span = depth.new_tensor(_scalar(near)), depth.new_tensor(_scalar(far) - _scalar(near))
+                    grey = ((depth - lo) / span) * mask.to(torch.float32)
+                    sink.submit(paths[0], rgb)
+                    sink.submit(paths[1], grey[..., None].expand(height, width, 3))
+                rendered.append(i)
+                for k, v in (("rgb", rgb), ("depth", depth), ("mask", mask), ("face", ex["face"])):
+                    frames.setdefault(k, []).append(v.detach())
+        finally:
+            if shared is None:
+                sink.close()
+        out = {k: torch.stack(v, 0).cpu().numpy() for k, v in frames.items()}
+        out["rendered"], out["skipped"] = rendered, skipped
+        return out
+
     def build_occupancy(self, networks, *, bounds, resolution, threshold, shapeCodes, expType=20, expCodes=None, dilate=1, netchunk=None):
         """Occupancy grid for ``render_rays(..., occupancy=...)``: the density of each of ``networks`` (one network or a sequence,
         normally coarse and fine) from :meth:`query_density` on the lattice ``bounds`` x ``resolution``; a cell is occupied iff one of

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""Measure iso-levels: extract the face's mesh at one or several density levels (``Renderer.extract_mesh``), rasterise each from a pose
+(``Renderer.render_mesh``, the GPU z-buffer of ``mesh.rasterize``), render the volume's own surface from the same pose ONCE
+(``Renderer.render_geometry(median=True, ndc=False)``) and print, per level, how well the two agree (``mesh.depth_agreement``: mask IoU,
+pixel counts, median and 95th-percentile |depth difference| on the overlap) next to the time of each stage.  The rasterised depth and the
+volume's depth are the same quantity: the ray parameter of the pixel's ``get_rays`` ray.
+
+Writes ``level_<level>_mesh.png`` (head-light shade) and ``level_<level>_mesh_depth.png`` per level and ``volume_depth.png`` into
+``--out``; prints one JSON line at the end.
+
+Networks come from a checkpoint (``--ckpt``) or seeded synthetic weights (``--synthetic DC WC DF WF``), codes from ``--fit`` or
+``synth.codes`` — the options of tools/render_geometry.py.  ON SEEDED WEIGHTS THE AGREEMENT NUMBERS MEAN NOTHING ABOUT A TRAINED FACE:
+a seeded network's density is noise, and the tool says so in its output; the stage times do not depend on the weights' values.
+
+  python tools/render_mesh.py --synthetic 8 256 10 1024 --bounds -4 -4 -4 4 4 4 --resolution 129 129 129 --levels 0,0.5,1 --size 512
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from mofanerf_amd import mesh, synth  # noqa: E402
+from mofanerf_amd.io import PngSink  # noqa: E402
+from mofanerf_amd.rays import pose_spherical  # noqa: E402
+from render_culled import load  # noqa: E402
+
+
+def median_ms(fn, warmup, frames):
+    """(median ms, every ms, the last result) of ``fn`` after ``warmup`` calls; each call ends with a device synchronisation."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms, out = [], None
+    for _ in range(max(frames, 1)):
+        t = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t) * 1e3)
+    return round(statistics.median(ms), 3), [round(v, 3) for v in ms], out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--ckpt", help="checkpoint directory (the newest *.tar is used) or one .tar file")
+    src.add_argument("--synthetic", type=int, nargs=4, metavar=("DC", "WC", "DF", "WF"), help="seeded synthetic coarse / fine networks")
+    ap.add_argument("--fit", help="saving_Parameters.tar of run_fit.py (shape / texture / expression codes); default synth.codes")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--bounds", type=float, nargs=6, required=True, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
+    ap.add_argument("--resolution", type=int, nargs=3, default=[129, 129, 129], metavar=("NX", "NY", "NZ"))
+    ap.add_argument("--brick", type=int, default=None, help="narrow-band extraction with bricks of B^3 cells (4, 8 or 16)")
+    lv = ap.add_mutually_exclusive_group(required=True)
+    lv.add_argument("--level", type=float, help="one iso-level of the pre-ReLU density (no default: none has been measured)")
+    lv.add_argument("--levels", help="several, comma-separated: a,b,c")
+    ap.add_argument("--size", type=int, default=512, help="frame height = width")
+    ap.add_argument("--samples", type=int, nargs=2, default=[64, 128], metavar=("N_SAMPLES", "N_IMPORTANCE"))
+    ap.add_argument("--near", type=float, default=8.0)
+    ap.add_argument("--far", type=float, default=26.0)
+    ap.add_argument("--chunk", type=int, default=196608)
+    ap.add_argument("--netchunk", type=int, default=196608)
+    ap.add_argument("--angle", type=float, default=25.0, help="azimuth of the view in degrees")
+    ap.add_argument("--radius", type=float, default=16.0, help="distance of the camera from the origin")
+    ap.add_argument("--acc-min", type=float, default=0.5, help="the volume's mask: acc >= this")
+    ap.add_argument("--median-threshold", type=float, default=0.5, help="the accumulated weight the volume's median depth is taken at")
+    ap.add_argument("--znear", type=float, default=1e-3)
+    ap.add_argument("--frames", type=int, default=5, help="timed frames per stage (the median is reported)")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default="mesh_out")
+    a = ap.parse_args(argv)
+    levels = [a.level] if a.levels is None else [float(v) for v in a.levels.split(",") if v.strip()]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    render, kw, bm, uv, exp = load(a, dev)
+    net = kw["network_fine"] if kw.get("network_fine") is not None else kw["network_fn"]
+    H = a.size
+    K = synth.intrinsics(H, H)
+    pose = pose_spherical(a.angle, 0.0, a.radius)[:3, :4]
+    kw = {k: v for k, v in dict(kw, near=a.near, far=a.far).items() if k != "ndc"}
+    bounds = (tuple(a.bounds[:3]), tuple(a.bounds[3:]))
+    if a.synthetic:
+        print("seeded synthetic weights: the agreement numbers below say NOTHING about a trained face (only the times carry over)", flush=True)
+
+    def volume():
+        out = render.render_geometry(H, H, K, chunk=a.chunk, c2w=pose, ndc=False, shapeCodes=bm, expType=20, expCodes=exp, median=True,
+                                     acc_min=a.acc_min, median_threshold=a.median_threshold, **kw)
+        render.check_launches(block=True)
+        return out
+
+    t_vol, all_vol, (_, _, acc, ex) = median_ms(volume, a.warmup, a.frames)
+    depth_vol = ex["depth_median"]
+    print(f"volume: render_geometry(median=True) {H} x {H}, {a.samples[0]} + {a.samples[1]} samples: {t_vol:.2f} ms per frame "
+          f"(median of {len(all_vol)}), {int((acc >= a.acc_min).sum())} pixels with acc >= {a.acc_min}", flush=True)
+    os.makedirs(a.out, exist_ok=True)
+    span = torch.full_like(depth_vol, a.far - a.near)
+    rows = []
+    with PngSink() as sink:
+        sink.submit(os.path.join(a.out, "volume_depth.png"), (((depth_vol - a.near) / span) * (acc >= a.acc_min))[..., None].expand(H, H, 3))
+        for level in levels:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            verts, faces = render.extract_mesh(net, bounds=bounds, resolution=tuple(a.resolution), level=level, shapeCodes=bm, expType=20,
+                                               expCodes=exp, netchunk=a.netchunk, brick=a.brick)[:2]
+            torch.cuda.synchronize()
+            t_extract = (time.perf_counter() - t0) * 1e3
+            t_mesh, all_mesh, (rgb, depth, mask, mex) = median_ms(
+                lambda: render.render_mesh(H, H, K, pose, verts, faces, znear=a.znear), a.warmup, a.frames)
+            t_raster, _, _ = median_ms(lambda: mesh.rasterize(verts, faces, H, H, K, pose, znear=a.znear), a.warmup, a.frames)
+            agree = mesh.depth_agreement(depth, mask, depth_vol, acc, a.acc_min)
+            drawn, culled, degenerate, wave = (int(v) for v in mex["counts"].cpu())
+            row = {"level": level, "V": int(verts.shape[0]), "F": int(faces.shape[0]), "extract_ms": round(t_extract, 2), "render_mesh_ms": t_mesh,
+                   "render_mesh_ms_all": all_mesh, "rasterize_ms": t_raster, "faces_drawn": drawn, "faces_culled": culled,
+                   "faces_degenerate": degenerate, "faces_wave_path": wave, **agree}
+            rows.append(row)
+            print(f"level {level:g}: V = {row['V']}, F = {row['F']} (culled {culled}, degenerate {degenerate}, wavefront path {wave}); extract "
+                  f"{t_extract:.1f} ms, render_mesh {t_mesh:.3f} ms (rasterize alone {t_raster:.3f} ms) against the volume's {t_vol:.1f} ms; "
+                  f"IoU {agree['iou']:.4f} (mesh {agree['n_mesh']}, volume {agree['n_vol']}, both {agree['n_both']}), |depth difference| median "
+                  f"{agree['median_abs']:.5f}, 95 % {agree['p95_abs']:.5f}", flush=True)
+            if culled:
+                print(f"  {culled} faces were culled whole (a vertex nearer than znear or outside the guard band): there is no near-plane clipping")
+            stem = os.path.join(a.out, f"level_{level:g}")
+            sink.submit(stem + "_mesh.png", rgb)
+            sink.submit(stem + "_mesh_depth.png", (((depth - a.near) / span) * mask)[..., None].expand(H, H, 3))
+    print(json.dumps({"size": H, "samples": a.samples, "angle": a.angle, "radius": a.radius, "near": a.near, "far": a.far, "acc_min": a.acc_min,
+                      "median_threshold": a.median_threshold, "resolution": a.resolution, "brick": a.brick,
+                      "wave_min_pixels": mesh.WAVE_MIN_PIXELS, "synthetic_weights": bool(a.synthetic),
+                      "agreement_says_nothing_about_a_trained_face": bool(a.synthetic), "render_geometry_ms": t_vol,
+                      "render_geometry_ms_all": all_vol, "levels": rows, "out": a.out}))
+
+
+if __name__ == "__main__":
+    main()
