@@ -479,7 +479,15 @@ int mofa_point_normals(const float* points, const float* acc, const float* rays_
 
 /* sample_pdf on (z_mid, weights[1:-1]) + sort(cat(z, z_samples)) + std(z_samples)
  * (render_class.py:324-328,345; tools/run_nerf_helpers.py:203-247).  u: [n_rays,Ni] (stride Ni) or a
- * shared row (stride 0) — linspace(0,1,Ni) for det. */
+ * shared row (stride 0) — linspace(0,1,Ni) for det.
+ * The arithmetic, one fp32 rounding per operation (no fused multiply-add, correctly rounded division): bins_i = 0.5f * (z[i+1] + z[i]);
+ * wp = w + 1e-5f over the interior weights w[1 .. S-2] (w[0] and w[S-1] are not read); wsum = (float)(fp64 sum of wp); pdf = wp / wsum;
+ * cdf_0 = 0, cdf_k = (float)(fp64 sum of pdf_0 .. pdf_{k-1}); lo = the first index with cdf > u, below = max(lo - 1, 0),
+ * above = min(lo, B - 1); den = cdf[above] - cdf[below], replaced by 1 when < 1e-5f; t = (u - cdf[below]) / den;
+ * z_samples = bins[below] + t * (bins[above] - bins[below]).  z_std = (float)sqrt of the fp64 population variance of the row's samples
+ * (0 for Ni = 1).  A NaN interior weight makes every sample of its ray, and z_std, NaN.
+ * z_fine is the STABLE sort of cat(z, z_samples) along the ray: equal values keep their order in the concatenation, every NaN comes
+ * after every number, NaNs in their order in the concatenation (torch.sort's order).  Every slot of z_fine is written for any input. */
 int mofa_sample_pdf_merge(const float* z, int64_t z_row_stride, const float* weights, const float* u,
                           int64_t u_row_stride, int64_t n_rays, int32_t S, int32_t Ni, float* z_samples,
                           float* z_fine, float* z_std, void* stream);

@@ -604,9 +604,11 @@ __global__ __launch_bounds__(256) void k_sample_pdf_merge(const float* __restric
     if (lane == 0 && z_std) z_std[ray] = (float)sqrt(m2 / (double)Ni);
     if (BINS || !z_fine) return;
 
-    // merge by rank: position = #(smaller) + #(equal with a lower index) — torch.sort's result for ANY input (the stochastic mode's
-    // samples arrive unsorted).  When both runs are already non-decreasing (always the coarse positions; the new samples whenever u
-    // is — the det mode's linspace — up to an ulp at a bin edge, which is why it is CHECKED, not assumed) the same rank is
+    // merge by rank: position = #(smaller) + #(equal with a lower index), a NaN after every number and behind the NaNs of a lower index —
+    // torch.sort's result for ANY input (the stochastic mode's samples arrive unsorted; NaN compares false both ways, so without its own
+    // rule every NaN would claim slot 0 and leave the row's last slots unwritten).  When both runs are already non-decreasing (always the
+    // coarse positions; the new samples whenever u is — the det mode's linspace — up to an ulp at a bin edge, which is why it is CHECKED,
+    // not assumed) the same rank is
     //   coarse e:  e + #(samples < v)        sample j:  j + #(coarse <= v)
     // i.e. one binary search per element (7 dependent LDS reads) instead of a pass over all N positions (round 6: the O(N^2) pass was
     // two thirds of this kernel's instructions; NaN fails the check and takes the general pass).
@@ -614,7 +616,9 @@ __global__ __launch_bounds__(256) void k_sample_pdf_merge(const float* __restric
     bool runs_sorted = true;
     for (int e = lane; e < N; e += 64) {
         const int last = e < S ? S - 1 : N - 1;
-        if (e < last) runs_sorted = runs_sorted && (all[e] <= all[e + 1]);
+        const float v = all[e];
+        // a run's last element has no neighbour to fail against: without v == v a lone NaN sample (Ni = 1) would pass
+        runs_sorted = runs_sorted && (e < last ? v <= all[e + 1] : v == v);
     }
     if (__all(runs_sorted ? 1 : 0)) {
         for (int e = lane; e < N; e += 64) {
@@ -641,9 +645,16 @@ __global__ __launch_bounds__(256) void k_sample_pdf_merge(const float* __restric
     for (int e = lane; e < N; e += 64) {
         const float v = all[e];
         int rank = 0;
-        for (int k = 0; k < N; ++k) {
-            const float o = all[k];
-            rank += (o < v || (o == v && k < e)) ? 1 : 0;
+        if (v == v) {
+            for (int k = 0; k < N; ++k) {
+                const float o = all[k];
+                rank += (o < v || (o == v && k < e)) ? 1 : 0;
+            }
+        } else {
+            for (int k = 0; k < N; ++k) {
+                const float o = all[k];
+                rank += (o == o || k < e) ? 1 : 0;
+            }
         }
         z_fine[ray * (long long)N + rank] = v;
     }
