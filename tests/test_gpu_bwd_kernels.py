@@ -192,9 +192,10 @@ def test_backward_data_against_fp64(gk, ko, Mp):
 
 
 # ---- mofa_layer_forward_masked ------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("Np,K", [(128, 64), (192, 64), (128, 48)])
+@pytest.mark.parametrize("Np,K", [(128, 64), (192, 64), (128, 48), (64, 64), (128, 32), (128, 1024)])
 def test_layer_forward_masked_bits(Np, K):
-    """The mask-writing forward (the contiguous-store epilogue at 128 x 64, the pass over y elsewhere): y bit-identical to
+    """The mask-writing forward (the contiguous-store epilogue at 128 x 64 and 128 x 1024, the pass over y elsewhere — the 64-feature tile, an odd panel
+    count, fewer than four panels; tests/test_gpu_fwd_kernels.py repeats the word-for-word check at every shape of its layer test): y bit-identical to
     mofa_layer_forward, every word of mask_bits_out = (y > 0) per the tape's layout, and the bits fed to the backward give what y gives."""
     gen = _gen(Np + K)
     st = lib.stream()
@@ -308,17 +309,17 @@ def test_bias_grad_rays(R, S, N):
 
 # ---- positional encoding: backward (rays, explicit points) and the feature panels ---------------------------------------------------------
 @pytest.mark.parametrize("R,S,zs", [(1, 1, 1), (5, 37, 41), (9, 130, 130), (130, 64, 64)])
-@pytest.mark.parametrize("nf", [0, 4, 10])
+@pytest.mark.parametrize("nf", [0, 4, 10, 16])
 def test_pe_backward_and_panels(nf, R, S, zs):
     """gx = g_id + sum_f 2^f (g_sin cos(2^f x) - g_cos sin(2^f x)) at the fp32 points x = o + d z; d_rays_o = sum_s gx, d_rays_d = sum_s gx z.
     Bound: 1e-6 * sum |terms| + C_PE * 2^-24 * sum_f 2^f (|g_sin| + |g_cos|), the second term for the device sincosf at arguments up to
-    2^9 |x|.  Measured on MI355X: worst |err| / (2^-24 * sum_f 2^f (|g_sin| + |g_cos|)) = 1.953 (d_pts at n_freqs = 4, 9 x 130; <= 0.38 for
+    2^9 |x| (2^15 |x| at 16 frequencies).  Measured on MI355X: worst |err| / (2^-24 * sum_f 2^f (|g_sin| + |g_cos|)) = 1.953 (d_pts at n_freqs = 4, 9 x 130; <= 0.38 for
     the summed ray outputs); C_PE = 7.8 = 4 x that ratio (bwd_reference.C_PE).  Worst err / sum |terms|: 1.5e-7.  (5, 37) runs with z_row_stride > S;
     S = 130: a lane takes several samples; 130 rays: more than one block's waves."""
     gen = _gen(nf + R + S)
     st = lib.stream()
     n, kp = R * S, L().mofa_pe_k_padded(nf)
-    assert kp == 64
+    assert kp == (64 if nf <= 10 else 128)                                             # 16 frequencies: 99 features in 8 panels
     Mp = br.round_up(n, 256)
     o = torch.rand(R, 3, generator=gen, device=DEV) * 6 - 3
     d = _randn(gen, R, 3, scale=0.6)
