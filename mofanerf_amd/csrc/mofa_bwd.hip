@@ -4,6 +4,7 @@
 // Built with -ffp-contract=off like the forward.
 #include <type_traits>
 
+#include "mofa_composite.h"
 #include "mofa_layer.h"
 #include "mofa_wgrad.h"
 
@@ -16,14 +17,6 @@ int mofa_internal_wgrad_reduce(const float* partial, int splits, int n_padded, i
 
 namespace mofa {
 namespace {
-
-constexpr int kWavesPerBlock = 4;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- head backward: dX[m][k] (+)= sum_o d_raw[m][off+o] * w[o][k], optionally * (saved > 0) -------------------
 // one thread per (point, 16-byte chunk of features); dx in panels [kp][m_padded][16].
@@ -255,116 +248,114 @@ __global__ __launch_bounds__(256) void k_pe_backward(const float* __restrict__ d
 // ---- raw2outputs backward (models/render_class.py:440-482) ---------------------------------------------------
 // w_i = alpha_i T_i, T_i = prod_{j<i}(1 - alpha_j + 1e-10).  With G_i = dL/dw_i (collected from rgb, depth, acc, disp and
 // the explicit weights gradient):  dL/dalpha_j = G_j T_j - (sum_{i>j} G_i w_i) / (1 - alpha_j + 1e-10).
-template <int SPL>
-__global__ __launch_bounds__(256) void k_composite_backward(
-    const float* __restrict__ raw, const float* __restrict__ z, long long z_row_stride, const float* __restrict__ rays_d,
-    const float* __restrict__ noise, long long n_rays, int S, int white_bkgd, const float* __restrict__ g_rgb,
-    const float* __restrict__ g_disp, const float* __restrict__ g_acc, const float* __restrict__ g_depth,
-    const float* __restrict__ g_weights, float* __restrict__ d_raw, float* __restrict__ d_rays_d) {
-    const int lane = threadIdx.x & 63;
-    const long long ray = (long long)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    if (ray >= n_rays) return;
-    const float dx = rays_d[ray * 3], dy = rays_d[ray * 3 + 1], dz = rays_d[ray * 3 + 2];
-    const float dnorm = __fsqrt_rn(dx * dx + dy * dy + dz * dz);
-    const float* zr = z + ray * z_row_stride;
-    const f32x4* rr = (const f32x4*)(raw + ray * (long long)S * 4);
+// The forward is recomputed by mofa_composite.h's pass (the same source lines k_composite runs, so the same alpha, T and w).
 
-    float zv[SPL + 1], alpha[SPL], sig[SPL], dlt[SPL], cr[SPL], cg[SPL], cb[SPL];
-    const int s0 = lane * SPL;
-#pragma unroll
-    for (int t = 0; t <= SPL; ++t) zv[t] = (s0 + t < S) ? zr[s0 + t] : 0.f;
-    float run = 1.0f;
+// sweep 1 of a slice: its terms of the ray's depth and acc, the forward sums the disp gradient needs
+template <int SPL>
+__device__ __forceinline__ void bwd_ray_sums(const CompRay& r, const CompSlice<SPL>& p, float T, float& sd, float& sa) {
 #pragma unroll
     for (int t = 0; t < SPL; ++t) {
-        const int s = s0 + t;
-        if (s < S) {
-            const f32x4 v = rr[s];
-            dlt[t] = (s + 1 < S) ? (zv[t + 1] - zv[t]) : 1e10f;
-            float sg = v.w;
-            if (noise) sg = sg + noise[ray * (long long)S + s];
-            sig[t] = sg;                                   // pre-ReLU (sign decides the gate)
-            alpha[t] = 1.0f - expf(-relu_np(sg) * (dlt[t] * dnorm));
-            cr[t] = 1.0f / (1.0f + expf(-v.x)), cg[t] = 1.0f / (1.0f + expf(-v.y)), cb[t] = 1.0f / (1.0f + expf(-v.z));
-            run = run * ((1.0f - alpha[t]) + 1e-10f);
-        } else {
-            alpha[t] = 0.f, sig[t] = 0.f, dlt[t] = 0.f, cr[t] = cg[t] = cb[t] = 0.f;
-        }
+        const float w = p.alpha[t] * T;
+        if (p.s0 + t < r.S) sd += w * p.zv[t], sa += w;
+        T = T * ((1.0f - p.alpha[t]) + 1e-10f);
     }
-    float incl = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl = incl * up;
-    }
-    float T0 = __shfl_up(incl, 1, 64);
-    if (lane == 0) T0 = 1.0f;
+}
 
-    // forward sums needed by the disp gradient
-    float T = T0, sd = 0.f, sa = 0.f;
-    float w[SPL], Tt[SPL];
+// the ray's part of G_i: the gradients of rgb, and of depth and acc with disp's and the white background's share folded in
+struct RayGrads {
+    float r, g, b, depth, acc;
+};
+__device__ __forceinline__ RayGrads bwd_ray_grads(const CompRay& r, float sd, float sa, int white_bkgd, const float* __restrict__ g_rgb,
+                                                  const float* __restrict__ g_disp, const float* __restrict__ g_acc,
+                                                  const float* __restrict__ g_depth) {
+    sd = wave_sum(sd), sa = wave_sum(sa);
+    RayGrads g;
+    g.r = g_rgb[r.ray * 3], g.g = g_rgb[r.ray * 3 + 1], g.b = g_rgb[r.ray * 3 + 2];
+    g.depth = g_depth ? g_depth[r.ray] : 0.f, g.acc = g_acc ? g_acc[r.ray] : 0.f;
+    const float gdisp = g_disp ? g_disp[r.ray] : 0.f;
+    if (gdisp != 0.f) {                                     // disp = acc/depth where depth/acc > 1e-10
+        const float q = __fdiv_rn(sd, sa);
+        if (q > 1e-10f) g.depth += gdisp * (-sa / (sd * sd)), g.acc += gdisp * (1.0f / sd);
+        else if (q != q) g.depth += q, g.acc += q;           // NaN propagates like autograd through 0/0
+    }
+    if (white_bkgd) g.acc -= g.r + g.g + g.b;                // rgb += 1 - acc
+    return g;
+}
+
+// sweep 2 of a slice: G_i, the suffix sums of G_i w_i, d_raw.  CARRY (the long form, walked back to front): `behind` is the sum of
+// G_i w_i over every later pass and leaves with this pass's added; the short form does not touch it.  dn_acc collects d L / d |rays_d|.
+template <int SPL, bool CARRY>
+__device__ __forceinline__ void bwd_slice(const CompRay& r, const CompSlice<SPL>& p, float T, const RayGrads& g,
+                                          const float* __restrict__ g_weights, float* __restrict__ d_raw, float& behind, float& dn_acc) {
+    float w[SPL], Tt[SPL], G[SPL], local = 0.f;
 #pragma unroll
     for (int t = 0; t < SPL; ++t) {
         Tt[t] = T;
-        w[t] = alpha[t] * T;
-        if (s0 + t < S) sd += w[t] * zv[t], sa += w[t];
-        T = T * ((1.0f - alpha[t]) + 1e-10f);
-    }
-    sd = wave_sum(sd), sa = wave_sum(sa);
-    const float gr = g_rgb[ray * 3], gg = g_rgb[ray * 3 + 1], gb = g_rgb[ray * 3 + 2];
-    float gdepth = g_depth ? g_depth[ray] : 0.f, gacc = g_acc ? g_acc[ray] : 0.f;
-    const float gdisp = g_disp ? g_disp[ray] : 0.f;
-    if (gdisp != 0.f) {                                     // disp = acc/depth where depth/acc > 1e-10
-        const float q = __fdiv_rn(sd, sa);
-        if (q > 1e-10f) gdepth += gdisp * (-sa / (sd * sd)), gacc += gdisp * (1.0f / sd);
-        else if (q != q) gdepth += q, gacc += q;             // NaN propagates like autograd through 0/0
-    }
-    if (white_bkgd) gacc -= gr + gg + gb;                    // rgb += 1 - acc
-
-    // G_i and the suffix sums of G_i w_i
-    float G[SPL], local = 0.f;
-#pragma unroll
-    for (int t = 0; t < SPL; ++t) {
-        const int s = s0 + t;
-        G[t] = (s < S) ? ((g_weights ? g_weights[ray * (long long)S + s] : 0.f) + gr * cr[t] + gg * cg[t] + gb * cb[t] +
-                          gdepth * zv[t] + gacc)
-                       : 0.f;
+        w[t] = p.alpha[t] * T;
+        T = T * ((1.0f - p.alpha[t]) + 1e-10f);
+        const int s = p.s0 + t;
+        G[t] = (s < r.S) ? ((g_weights ? g_weights[r.row + s] : 0.f) + g.r * p.cr[t] + g.g * p.cg[t] + g.b * p.cb[t] +
+                            g.depth * p.zv[t] + g.acc)
+                         : 0.f;
         local += G[t] * w[t];
     }
     float suf = local;                                      // inclusive suffix sum over lanes
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const float dn = __shfl_down(suf, o, 64);
-        if (lane + o < 64) suf += dn;
+        if (r.lane + o < 64) suf += dn;
     }
     float after = __shfl_down(suf, 1, 64);                  // sum over lanes > this one
-    if (lane == 63) after = 0.f;
-
-    float dn_acc = 0.f;                                     // d L / d |rays_d|
+    if (r.lane == 63) after = 0.f;
+    if constexpr (CARRY) {
+        after += behind;
+        behind += __shfl(suf, 0, 64);
+    }
 #pragma unroll
     for (int t = SPL - 1; t >= 0; --t) {
-        const int s = s0 + t;
-        if (s < S) {
-            const float one_m = (1.0f - alpha[t]) + 1e-10f;
+        const int s = p.s0 + t;
+        if (s < r.S) {
+            const float one_m = (1.0f - p.alpha[t]) + 1e-10f;
             const float dalpha = G[t] * Tt[t] - after / one_m;
-            const float dist = dlt[t] * dnorm;
-            const float keep = 1.0f - alpha[t];             // exp(-sigma dist)
-            const float dsig = sig[t] > 0.f ? dalpha * dist * keep : 0.f;
-            const float ddist = dalpha * relu_np(sig[t]) * keep;
-            dn_acc += ddist * dlt[t];
+            const float dist = p.dlt[t] * r.dnorm;
+            const float keep = 1.0f - p.alpha[t];           // exp(-sigma dist)
+            const float dsig = p.sig[t] > 0.f ? dalpha * dist * keep : 0.f;
+            const float ddist = dalpha * relu_np(p.sig[t]) * keep;
+            dn_acc += ddist * p.dlt[t];
             f32x4 o;
-            o.x = w[t] * gr * cr[t] * (1.0f - cr[t]);
-            o.y = w[t] * gg * cg[t] * (1.0f - cg[t]);
-            o.z = w[t] * gb * cb[t] * (1.0f - cb[t]);
+            o.x = w[t] * g.r * p.cr[t] * (1.0f - p.cr[t]);
+            o.y = w[t] * g.g * p.cg[t] * (1.0f - p.cg[t]);
+            o.z = w[t] * g.b * p.cb[t] * (1.0f - p.cb[t]);
             o.w = dsig;
-            *(f32x4*)(d_raw + (ray * (long long)S + s) * 4) = o;
+            *(f32x4*)(d_raw + (r.row + s) * 4) = o;
             after += G[t] * w[t];
         }
     }
+}
+
+__device__ __forceinline__ void bwd_finish(const CompRay& r, float dn_acc, float* __restrict__ d_rays_d) {
     dn_acc = wave_sum(dn_acc);
-    if (lane == 0 && d_rays_d) {
-        const float inv = dnorm > 0.f ? 1.0f / dnorm : 0.f;
-        d_rays_d[ray * 3] = dn_acc * dx * inv, d_rays_d[ray * 3 + 1] = dn_acc * dy * inv, d_rays_d[ray * 3 + 2] = dn_acc * dz * inv;
+    if (r.lane == 0 && d_rays_d) {
+        const float inv = r.dnorm > 0.f ? 1.0f / r.dnorm : 0.f;
+        d_rays_d[r.ray * 3] = dn_acc * r.dx * inv, d_rays_d[r.ray * 3 + 1] = dn_acc * r.dy * inv, d_rays_d[r.ray * 3 + 2] = dn_acc * r.dz * inv;
     }
+}
+
+template <int SPL>
+__global__ __launch_bounds__(256) void k_composite_backward(
+    const float* __restrict__ raw, const float* __restrict__ z, long long z_row_stride, const float* __restrict__ rays_d,
+    const float* __restrict__ noise, long long n_rays, int S, int white_bkgd, const float* __restrict__ g_rgb,
+    const float* __restrict__ g_disp, const float* __restrict__ g_acc, const float* __restrict__ g_depth,
+    const float* __restrict__ g_weights, float* __restrict__ d_raw, float* __restrict__ d_rays_d) {
+    CompRay r;
+    if (!comp_ray<true>(r, raw, z, z_row_stride, rays_d, noise, n_rays, S)) return;
+    CompSlice<SPL> p;
+    float one = 1.0f, sd = 0.f, sa = 0.f, behind = 0.f, dn_acc = 0.f;   // (one pass: `one` and `behind` are not touched)
+    const float T0 = comp_lane_T<false>(comp_load<SPL, true>(r, 0, p), r.lane, one);
+    bwd_ray_sums(r, p, T0, sd, sa);
+    const RayGrads g = bwd_ray_grads(r, sd, sa, white_bkgd, g_rgb, g_disp, g_acc, g_depth);
+    bwd_slice<SPL, false>(r, p, T0, g, g_weights, d_raw, behind, dn_acc);
+    bwd_finish(r, dn_acc, d_rays_d);
 }
 
 // Rays with more than 256 samples: the same backward walked in passes of 256 samples (lane l owns samples [256 p + 4 l, +4) of
@@ -379,135 +370,29 @@ __global__ __launch_bounds__(256) void k_composite_backward_long(
     const float* __restrict__ g_weights, float* __restrict__ d_raw, float* __restrict__ d_rays_d) {
     constexpr int SPL = 4;
     __shared__ float s_carry[kWavesPerBlock][kMaxPasses];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const long long ray = (long long)blockIdx.x * kWavesPerBlock + wv;
-    if (ray >= n_rays) return;                              // wave-uniform; only wave-level synchronisation below
-    const float dx = rays_d[ray * 3], dy = rays_d[ray * 3 + 1], dz = rays_d[ray * 3 + 2];
-    const float dnorm = __fsqrt_rn(dx * dx + dy * dy + dz * dz);
-    const float* zr = z + ray * z_row_stride;
-    const f32x4* rr = (const f32x4*)(raw + ray * (long long)S * 4);
-    const int passes = (S + 64 * SPL - 1) / (64 * SPL);
-
-    float zv[SPL + 1], alpha[SPL], sig[SPL], dlt[SPL], cr[SPL], cg[SPL], cb[SPL];
-    auto load_pass = [&](int pass) -> float {               // fills the per-sample arrays; returns this lane's (1 - alpha + 1e-10) product
-        const int s0 = pass * 64 * SPL + lane * SPL;
-#pragma unroll
-        for (int t = 0; t <= SPL; ++t) zv[t] = (s0 + t < S) ? zr[s0 + t] : 0.f;
-        float run = 1.0f;
-#pragma unroll
-        for (int t = 0; t < SPL; ++t) {
-            const int s = s0 + t;
-            if (s < S) {
-                const f32x4 v = rr[s];
-                dlt[t] = (s + 1 < S) ? (zv[t + 1] - zv[t]) : 1e10f;
-                float sg = v.w;
-                if (noise) sg = sg + noise[ray * (long long)S + s];
-                sig[t] = sg;
-                alpha[t] = 1.0f - expf(-relu_np(sg) * (dlt[t] * dnorm));
-                cr[t] = 1.0f / (1.0f + expf(-v.x)), cg[t] = 1.0f / (1.0f + expf(-v.y)), cb[t] = 1.0f / (1.0f + expf(-v.z));
-                run = run * ((1.0f - alpha[t]) + 1e-10f);
-            } else {
-                alpha[t] = 0.f, sig[t] = 0.f, dlt[t] = 0.f, cr[t] = cg[t] = cb[t] = 0.f;
-            }
-        }
-        return run;
-    };
-    auto lane_T0 = [&](float run, float carry, float& total) -> float {   // transmittance in front of this lane's first sample
-        float incl = run;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const float up = __shfl_up(incl, o, 64);
-            if (lane >= o) incl = incl * up;
-        }
-        float T0 = __shfl_up(incl, 1, 64);
-        if (lane == 0) T0 = 1.0f;
-        total = __shfl(incl, 63, 64);
-        return carry * T0;
-    };
+    CompRay r;
+    if (!comp_ray<true>(r, raw, z, z_row_stride, rays_d, noise, n_rays, S)) return;   // wave-uniform; only wave-level synchronisation below
+    const int wv = threadIdx.x >> 6, passes = (S + 64 * SPL - 1) / (64 * SPL);
+    CompSlice<SPL> p;
 
     // sweep 1: carries and the ray sums
     float carry = 1.0f, sd = 0.f, sa = 0.f;
     for (int pass = 0; pass < passes; ++pass) {
-        const float run = load_pass(pass);
-        if (lane == 0) s_carry[wv][pass] = carry;
-        float total;
-        float T = lane_T0(run, carry, total);
-        carry = carry * total;
-        const int s0 = pass * 64 * SPL + lane * SPL;
-#pragma unroll
-        for (int t = 0; t < SPL; ++t) {
-            const float w = alpha[t] * T;
-            if (s0 + t < S) sd += w * zv[t], sa += w;
-            T = T * ((1.0f - alpha[t]) + 1e-10f);
-        }
+        const float run = comp_load<SPL, true>(r, pass * 64 * SPL, p);
+        if (r.lane == 0) s_carry[wv][pass] = carry;
+        bwd_ray_sums(r, p, comp_lane_T<true>(run, r.lane, carry), sd, sa);
     }
     __builtin_amdgcn_wave_barrier();
-    sd = wave_sum(sd), sa = wave_sum(sa);
-    const float gr = g_rgb[ray * 3], gg = g_rgb[ray * 3 + 1], gb = g_rgb[ray * 3 + 2];
-    float gdepth = g_depth ? g_depth[ray] : 0.f, gacc = g_acc ? g_acc[ray] : 0.f;
-    const float gdisp = g_disp ? g_disp[ray] : 0.f;
-    if (gdisp != 0.f) {
-        const float q = __fdiv_rn(sd, sa);
-        if (q > 1e-10f) gdepth += gdisp * (-sa / (sd * sd)), gacc += gdisp * (1.0f / sd);
-        else if (q != q) gdepth += q, gacc += q;
-    }
-    if (white_bkgd) gacc -= gr + gg + gb;
+    const RayGrads g = bwd_ray_grads(r, sd, sa, white_bkgd, g_rgb, g_disp, g_acc, g_depth);
 
     // sweep 2: back to front
-    float behind = 0.f, dn_acc = 0.f;                       // sum of G_i w_i over every LATER pass; d L / d |rays_d|
+    float behind = 0.f, dn_acc = 0.f;
     for (int pass = passes - 1; pass >= 0; --pass) {
-        const float run = load_pass(pass);
-        float total;
-        const float T0 = lane_T0(run, s_carry[wv][pass], total);
-        const int s0 = pass * 64 * SPL + lane * SPL;
-        float T = T0, w[SPL], Tt[SPL], G[SPL], local = 0.f;
-#pragma unroll
-        for (int t = 0; t < SPL; ++t) {
-            Tt[t] = T;
-            w[t] = alpha[t] * T;
-            T = T * ((1.0f - alpha[t]) + 1e-10f);
-            const int s = s0 + t;
-            G[t] = (s < S) ? ((g_weights ? g_weights[ray * (long long)S + s] : 0.f) + gr * cr[t] + gg * cg[t] + gb * cb[t] +
-                              gdepth * zv[t] + gacc)
-                           : 0.f;
-            local += G[t] * w[t];
-        }
-        float suf = local;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const float dn = __shfl_down(suf, o, 64);
-            if (lane + o < 64) suf += dn;
-        }
-        float after = __shfl_down(suf, 1, 64);
-        if (lane == 63) after = 0.f;
-        after += behind;
-        behind += __shfl(suf, 0, 64);
-#pragma unroll
-        for (int t = SPL - 1; t >= 0; --t) {
-            const int s = s0 + t;
-            if (s < S) {
-                const float one_m = (1.0f - alpha[t]) + 1e-10f;
-                const float dalpha = G[t] * Tt[t] - after / one_m;
-                const float dist = dlt[t] * dnorm;
-                const float keep = 1.0f - alpha[t];
-                const float dsig = sig[t] > 0.f ? dalpha * dist * keep : 0.f;
-                const float ddist = dalpha * relu_np(sig[t]) * keep;
-                dn_acc += ddist * dlt[t];
-                f32x4 o;
-                o.x = w[t] * gr * cr[t] * (1.0f - cr[t]);
-                o.y = w[t] * gg * cg[t] * (1.0f - cg[t]);
-                o.z = w[t] * gb * cb[t] * (1.0f - cb[t]);
-                o.w = dsig;
-                *(f32x4*)(d_raw + (ray * (long long)S + s) * 4) = o;
-                after += G[t] * w[t];
-            }
-        }
+        const float run = comp_load<SPL, true>(r, pass * 64 * SPL, p);
+        float front = s_carry[wv][pass];                    // (comp_lane_T moves it on to the next pass; not needed again)
+        bwd_slice<SPL, true>(r, p, comp_lane_T<true>(run, r.lane, front), g, g_weights, d_raw, behind, dn_acc);
     }
-    dn_acc = wave_sum(dn_acc);
-    if (lane == 0 && d_rays_d) {
-        const float inv = dnorm > 0.f ? 1.0f / dnorm : 0.f;
-        d_rays_d[ray * 3] = dn_acc * dx * inv, d_rays_d[ray * 3 + 1] = dn_acc * dy * inv, d_rays_d[ray * 3 + 2] = dn_acc * dz * inv;
-    }
+    bwd_finish(r, dn_acc, d_rays_d);
 }
 
 // ---- head bias gradients: the four column sums of d_raw [n_points][4] (rgb head: columns 0..2, sigma head: column 3) in ONE pass ----

@@ -3,7 +3,7 @@
 // owns one ray so the sample buffer is read with fully coalesced 16-byte loads.
 // Built with -ffp-contract=off: the reference evaluates these formulas as separate aten ops, so no
 // multiply-add may be fused here (SURVEY.md §7 hard part 2).
-#include "mofa_common.h"
+#include "mofa_composite.h"
 
 extern "C" {   // mofa_mlp.hip: bracket a launch with HIP events when a measurement session is open (bench.py's HBM-side roofline)
 int mofa_internal_prof_open(void* stream, int kind);
@@ -13,18 +13,6 @@ void mofa_internal_prof_close(void* stream, int kind, double work);
 namespace mofa {
 namespace {
 
-constexpr int kWavesPerBlock = 4;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- get_rays (tools/run_nerf_helpers.py:153-168) + viewdirs (render_class.py:399-401) -------------
 // `pix_list` (may be NULL): flat pixel indices j * W + i of the n rays (fitting / training batches gather 1-4 k of the H*W
@@ -83,8 +71,7 @@ __global__ __launch_bounds__(256) void k_rays_pose_backward(int W, float fx, flo
 }
 
 // ---- raw2outputs (models/render_class.py:440-482) --------------------------------------------------
-// One wavefront per ray; lane l owns samples [l*SPL, l*SPL+SPL).  T_i = prod_{j<i} (1 - alpha_j + 1e-10)
-// is an in-lane running product combined with a 6-step wavefront exclusive prefix product.
+// One wavefront per ray; lane l owns samples [l*SPL, l*SPL+SPL).  The pass itself is mofa_composite.h's.
 template <int SPL>
 __global__ __launch_bounds__(256) void k_composite(const float* __restrict__ raw, const float* __restrict__ z,
                                                    long long z_row_stride, const float* __restrict__ rays_d,
@@ -92,73 +79,14 @@ __global__ __launch_bounds__(256) void k_composite(const float* __restrict__ raw
                                                    int white_bkgd, float* __restrict__ rgb_out,
                                                    float* __restrict__ disp_out, float* __restrict__ acc_out,
                                                    float* __restrict__ depth_out, float* __restrict__ weights_out) {
-    const int lane = threadIdx.x & 63;
-    const long long ray = (long long)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    if (ray >= n_rays) return;
-    const float dx = rays_d[ray * 3], dy = rays_d[ray * 3 + 1], dz = rays_d[ray * 3 + 2];
-    const float dnorm = __fsqrt_rn(dx * dx + dy * dy + dz * dz);
-    const float* zr = z + ray * z_row_stride;
-    const f32x4* rr = (const f32x4*)(raw + ray * (long long)S * 4);
-
-    float zv[SPL + 1], alpha[SPL], cr[SPL], cg[SPL], cb[SPL];
-    const int s0 = lane * SPL;
-#pragma unroll
-    for (int t = 0; t <= SPL; ++t) zv[t] = (s0 + t < S) ? zr[s0 + t] : 0.f;
-    float run = 1.0f;  // product of this lane's (1 - alpha + 1e-10)
-#pragma unroll
-    for (int t = 0; t < SPL; ++t) {
-        const int s = s0 + t;
-        if (s < S) {
-            const f32x4 v = rr[s];
-            float dist = (s + 1 < S) ? (zv[t + 1] - zv[t]) : 1e10f;
-            dist = dist * dnorm;
-            float sig = v.w;
-            if (noise) sig = sig + noise[ray * (long long)S + s];
-            sig = relu_np(sig);
-            alpha[t] = 1.0f - expf(-sig * dist);
-            cr[t] = 1.0f / (1.0f + expf(-v.x));
-            cg[t] = 1.0f / (1.0f + expf(-v.y));
-            cb[t] = 1.0f / (1.0f + expf(-v.z));
-            run = run * ((1.0f - alpha[t]) + 1e-10f);
-        } else {
-            alpha[t] = 0.f, cr[t] = cg[t] = cb[t] = 0.f;
-        }
-    }
-    // exclusive prefix product across lanes
-    float incl = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl = incl * up;
-    }
-    float T = __shfl_up(incl, 1, 64);
-    if (lane == 0) T = 1.0f;
-
-    float sr = 0.f, sg = 0.f, sb = 0.f, sd = 0.f, sa = 0.f;
-#pragma unroll
-    for (int t = 0; t < SPL; ++t) {
-        const int s = s0 + t;
-        if (s < S) {
-            const float w = alpha[t] * T;
-            weights_out[ray * (long long)S + s] = w;
-            sr += w * cr[t], sg += w * cg[t], sb += w * cb[t];
-            sd += w * zv[t];
-            sa += w;
-            T = T * ((1.0f - alpha[t]) + 1e-10f);
-        }
-    }
-    sr = wave_sum(sr), sg = wave_sum(sg), sb = wave_sum(sb), sd = wave_sum(sd), sa = wave_sum(sa);
-    if (lane == 0) {
-        if (white_bkgd) {
-            const float bg = 1.0f - sa;
-            sr += bg, sg += bg, sb += bg;
-        }
-        rgb_out[ray * 3] = sr, rgb_out[ray * 3 + 1] = sg, rgb_out[ray * 3 + 2] = sb;
-        const float q = __fdiv_rn(sd, sa);  // 0/0 -> NaN, and torch.max propagates it (render_class.py:476)
-        disp_out[ray] = (q != q) ? q : __fdiv_rn(1.0f, fmaxf(1e-10f, q));
-        acc_out[ray] = sa;
-        depth_out[ray] = sd;
-    }
+    CompRay r;
+    if (!comp_ray<true>(r, raw, z, z_row_stride, rays_d, noise, n_rays, S)) return;
+    CompSlice<SPL> p;
+    CompSums sum;
+    float carry = 1.0f;   // one pass: comp_lane_T<false> does not touch it
+    const float run = comp_load<SPL, true>(r, 0, p);
+    comp_accumulate<SPL, true>(r, p, comp_lane_T<false>(run, r.lane, carry), weights_out, sum);
+    comp_finish<true>(r, sum, white_bkgd, rgb_out, disp_out, acc_out, depth_out);
 }
 
 // Rays with more than 256 samples (the reference has no limit: N_samples / N_importance are free flags, tools/config_parser.py):
@@ -172,145 +100,36 @@ __global__ __launch_bounds__(256) void k_composite_long(const float* __restrict_
                                                         float* __restrict__ disp_out, float* __restrict__ acc_out,
                                                         float* __restrict__ depth_out, float* __restrict__ weights_out) {
     constexpr int SPL = 4;
-    const int lane = threadIdx.x & 63;
-    const long long ray = (long long)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    if (ray >= n_rays) return;
-    const float dx = rays_d[ray * 3], dy = rays_d[ray * 3 + 1], dz = rays_d[ray * 3 + 2];
-    const float dnorm = __fsqrt_rn(dx * dx + dy * dy + dz * dz);
-    const float* zr = z + ray * z_row_stride;
-    const f32x4* rr = (const f32x4*)(raw + ray * (long long)S * 4);
+    CompRay r;
+    if (!comp_ray<true>(r, raw, z, z_row_stride, rays_d, noise, n_rays, S)) return;
+    CompSums sum;
     float carry = 1.0f;                                   // transmittance in front of the current pass
-    float sr = 0.f, sg = 0.f, sb = 0.f, sd = 0.f, sa = 0.f;
     for (int base = 0; base < S; base += 64 * SPL) {
-        float zv[SPL + 1], alpha[SPL], cr[SPL], cg[SPL], cb[SPL];
-        const int s0 = base + lane * SPL;
-#pragma unroll
-        for (int t = 0; t <= SPL; ++t) zv[t] = (s0 + t < S) ? zr[s0 + t] : 0.f;
-        float run = 1.0f;
-#pragma unroll
-        for (int t = 0; t < SPL; ++t) {
-            const int s = s0 + t;
-            if (s < S) {
-                const f32x4 v = rr[s];
-                float dist = (s + 1 < S) ? (zv[t + 1] - zv[t]) : 1e10f;
-                dist = dist * dnorm;
-                float sig = v.w;
-                if (noise) sig = sig + noise[ray * (long long)S + s];
-                sig = relu_np(sig);
-                alpha[t] = 1.0f - expf(-sig * dist);
-                cr[t] = 1.0f / (1.0f + expf(-v.x));
-                cg[t] = 1.0f / (1.0f + expf(-v.y));
-                cb[t] = 1.0f / (1.0f + expf(-v.z));
-                run = run * ((1.0f - alpha[t]) + 1e-10f);
-            } else {
-                alpha[t] = 0.f, cr[t] = cg[t] = cb[t] = 0.f;
-            }
-        }
-        float incl = run;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const float up = __shfl_up(incl, o, 64);
-            if (lane >= o) incl = incl * up;
-        }
-        float T = __shfl_up(incl, 1, 64);
-        if (lane == 0) T = 1.0f;
-        T = carry * T;
-        carry = carry * __shfl(incl, 63, 64);
-#pragma unroll
-        for (int t = 0; t < SPL; ++t) {
-            const int s = s0 + t;
-            if (s < S) {
-                const float w = alpha[t] * T;
-                weights_out[ray * (long long)S + s] = w;
-                sr += w * cr[t], sg += w * cg[t], sb += w * cb[t];
-                sd += w * zv[t];
-                sa += w;
-                T = T * ((1.0f - alpha[t]) + 1e-10f);
-            }
-        }
+        CompSlice<SPL> p;
+        const float run = comp_load<SPL, true>(r, base, p);
+        comp_accumulate<SPL, true>(r, p, comp_lane_T<true>(run, r.lane, carry), weights_out, sum);
     }
-    sr = wave_sum(sr), sg = wave_sum(sg), sb = wave_sum(sb), sd = wave_sum(sd), sa = wave_sum(sa);
-    if (lane == 0) {
-        if (white_bkgd) {
-            const float bg = 1.0f - sa;
-            sr += bg, sg += bg, sb += bg;
-        }
-        rgb_out[ray * 3] = sr, rgb_out[ray * 3 + 1] = sg, rgb_out[ray * 3 + 2] = sb;
-        const float q = __fdiv_rn(sd, sa);
-        disp_out[ray] = (q != q) ? q : __fdiv_rn(1.0f, fmaxf(1e-10f, q));
-        acc_out[ray] = sa;
-        depth_out[ray] = sd;
-    }
+    comp_finish<true>(r, sum, white_bkgd, rgb_out, disp_out, acc_out, depth_out);
 }
 
 // ---- raw2outputs without colour: depth / acc / disp / weights from the density alone ------------------------------------------
-// The geometry-only render's compositing (mofa_composite_sigma).  `sigma [n_rays,S]` is raw[..., 3] (pre-ReLU) on its own.  Same
-// lane-to-sample assignment, same operations in the same order as k_composite / k_composite_long — dist * dnorm, relu, 1 - expf(-sig * dist),
-// the in-lane running product, the 6-step prefix product, wave_sum, __fdiv_rn, the NaN rule — so every output is the bits
-// mofa_composite_forward gives for a raw whose channel 3 is sigma (no multiply-add is fused in this translation unit).
+// The geometry-only render's compositing (mofa_composite_sigma).  `sigma [n_rays,S]` is raw[..., 3] (pre-ReLU) on its own.  These are
+// k_composite / k_composite_long instantiated without colour: the same pass, so every output is the bits mofa_composite_forward gives
+// for a raw whose channel 3 is sigma (no multiply-add is fused in this translation unit).
 template <int SPL>
 __global__ __launch_bounds__(256) void k_composite_sigma(const float* __restrict__ sigma, const float* __restrict__ z,
                                                          long long z_row_stride, const float* __restrict__ rays_d,
                                                          const float* __restrict__ noise, long long n_rays, int S,
                                                          float* __restrict__ disp_out, float* __restrict__ acc_out,
                                                          float* __restrict__ depth_out, float* __restrict__ weights_out) {
-    const int lane = threadIdx.x & 63;
-    const long long ray = (long long)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    if (ray >= n_rays) return;
-    const float dx = rays_d[ray * 3], dy = rays_d[ray * 3 + 1], dz = rays_d[ray * 3 + 2];
-    const float dnorm = __fsqrt_rn(dx * dx + dy * dy + dz * dz);
-    const float* zr = z + ray * z_row_stride;
-    const float* sr = sigma + ray * (long long)S;
-
-    float zv[SPL + 1], alpha[SPL];
-    const int s0 = lane * SPL;
-#pragma unroll
-    for (int t = 0; t <= SPL; ++t) zv[t] = (s0 + t < S) ? zr[s0 + t] : 0.f;
-    float run = 1.0f;  // product of this lane's (1 - alpha + 1e-10)
-#pragma unroll
-    for (int t = 0; t < SPL; ++t) {
-        const int s = s0 + t;
-        if (s < S) {
-            float dist = (s + 1 < S) ? (zv[t + 1] - zv[t]) : 1e10f;
-            dist = dist * dnorm;
-            float sig = sr[s];
-            if (noise) sig = sig + noise[ray * (long long)S + s];
-            sig = relu_np(sig);
-            alpha[t] = 1.0f - expf(-sig * dist);
-            run = run * ((1.0f - alpha[t]) + 1e-10f);
-        } else {
-            alpha[t] = 0.f;
-        }
-    }
-    // exclusive prefix product across lanes
-    float incl = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl = incl * up;
-    }
-    float T = __shfl_up(incl, 1, 64);
-    if (lane == 0) T = 1.0f;
-
-    float sd = 0.f, sa = 0.f;
-#pragma unroll
-    for (int t = 0; t < SPL; ++t) {
-        const int s = s0 + t;
-        if (s < S) {
-            const float w = alpha[t] * T;
-            weights_out[ray * (long long)S + s] = w;
-            sd += w * zv[t];
-            sa += w;
-            T = T * ((1.0f - alpha[t]) + 1e-10f);
-        }
-    }
-    sd = wave_sum(sd), sa = wave_sum(sa);
-    if (lane == 0) {
-        const float q = __fdiv_rn(sd, sa);  // 0/0 -> NaN, as in k_composite
-        disp_out[ray] = (q != q) ? q : __fdiv_rn(1.0f, fmaxf(1e-10f, q));
-        acc_out[ray] = sa;
-        depth_out[ray] = sd;
-    }
+    CompRay r;
+    if (!comp_ray<false>(r, sigma, z, z_row_stride, rays_d, noise, n_rays, S)) return;
+    CompSlice<SPL> p;
+    CompSums sum;
+    float carry = 1.0f;   // one pass: comp_lane_T<false> does not touch it
+    const float run = comp_load<SPL, false>(r, 0, p);
+    comp_accumulate<SPL, false>(r, p, comp_lane_T<false>(run, r.lane, carry), weights_out, sum);
+    comp_finish<false>(r, sum, 0, nullptr, disp_out, acc_out, depth_out);
 }
 
 // more than 256 samples: k_composite_long's passes of 256 samples (lane l owns samples [256 p + 4 l, +4) of pass p)
@@ -320,65 +139,16 @@ __global__ __launch_bounds__(256) void k_composite_sigma_long(const float* __res
                                                               float* __restrict__ disp_out, float* __restrict__ acc_out,
                                                               float* __restrict__ depth_out, float* __restrict__ weights_out) {
     constexpr int SPL = 4;
-    const int lane = threadIdx.x & 63;
-    const long long ray = (long long)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    if (ray >= n_rays) return;
-    const float dx = rays_d[ray * 3], dy = rays_d[ray * 3 + 1], dz = rays_d[ray * 3 + 2];
-    const float dnorm = __fsqrt_rn(dx * dx + dy * dy + dz * dz);
-    const float* zr = z + ray * z_row_stride;
-    const float* sr = sigma + ray * (long long)S;
+    CompRay r;
+    if (!comp_ray<false>(r, sigma, z, z_row_stride, rays_d, noise, n_rays, S)) return;
+    CompSums sum;
     float carry = 1.0f;                                   // transmittance in front of the current pass
-    float sd = 0.f, sa = 0.f;
     for (int base = 0; base < S; base += 64 * SPL) {
-        float zv[SPL + 1], alpha[SPL];
-        const int s0 = base + lane * SPL;
-#pragma unroll
-        for (int t = 0; t <= SPL; ++t) zv[t] = (s0 + t < S) ? zr[s0 + t] : 0.f;
-        float run = 1.0f;
-#pragma unroll
-        for (int t = 0; t < SPL; ++t) {
-            const int s = s0 + t;
-            if (s < S) {
-                float dist = (s + 1 < S) ? (zv[t + 1] - zv[t]) : 1e10f;
-                dist = dist * dnorm;
-                float sig = sr[s];
-                if (noise) sig = sig + noise[ray * (long long)S + s];
-                sig = relu_np(sig);
-                alpha[t] = 1.0f - expf(-sig * dist);
-                run = run * ((1.0f - alpha[t]) + 1e-10f);
-            } else {
-                alpha[t] = 0.f;
-            }
-        }
-        float incl = run;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const float up = __shfl_up(incl, o, 64);
-            if (lane >= o) incl = incl * up;
-        }
-        float T = __shfl_up(incl, 1, 64);
-        if (lane == 0) T = 1.0f;
-        T = carry * T;
-        carry = carry * __shfl(incl, 63, 64);
-#pragma unroll
-        for (int t = 0; t < SPL; ++t) {
-            const int s = s0 + t;
-            if (s < S) {
-                const float w = alpha[t] * T;
-                weights_out[ray * (long long)S + s] = w;
-                sd += w * zv[t];
-                sa += w;
-                T = T * ((1.0f - alpha[t]) + 1e-10f);
-            }
-        }
+        CompSlice<SPL> p;
+        const float run = comp_load<SPL, false>(r, base, p);
+        comp_accumulate<SPL, false>(r, p, comp_lane_T<true>(run, r.lane, carry), weights_out, sum);
     }
-    sd = wave_sum(sd), sa = wave_sum(sa);
-    if (lane == 0) {
-        const float q = __fdiv_rn(sd, sa);
-        disp_out[ray] = (q != q) ? q : __fdiv_rn(1.0f, fmaxf(1e-10f, q));
-        acc_out[ray] = sa;
-        depth_out[ray] = sd;
-    }
+    comp_finish<false>(r, sum, 0, nullptr, disp_out, acc_out, depth_out);
 }
 
 // ---- the points of a pass: p = o + d * z, multiply and add rounded separately (the point the network's layer-0 prologue forms) ----

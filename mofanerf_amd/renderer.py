@@ -262,10 +262,7 @@ class Renderer(torch.nn.Module):
         R, S = int(inputs.shape[0]), int(inputs.shape[1])
         h = self._hip(fn)
         want_w = (weight_grads is None or bool(weight_grads)) and any(l.weight.requires_grad or l.bias.requires_grad for l in h._linears)
-        rg = lambda t: torch.is_tensor(t) and t.requires_grad
-        needs_grad = torch.is_grad_enabled() and (want_w or rg(inputs) or rg(viewdirs) or rg(self.shapeCodes) or rg(self.decoding_texCodes) or
-                                                  rg(self.expCodes_Sigma[self.expType]) or
-                                                  any(q.requires_grad for q in unwrap(self.idSpecificMod).parameters()))
+        needs_grad = torch.is_grad_enabled() and (want_w or self._asks_grad(inputs, viewdirs))
         keep, self._weight_grads = self._weight_grads, want_w
         try:
             with torch.set_grad_enabled(needs_grad):
@@ -326,6 +323,74 @@ class Renderer(torch.nn.Module):
         self._folded_coarse = self._fold_codes(network_fn, self.decoding_texCodes).clone()
         self._folded_fine = self._fold_codes(network_fine, self.decoding_texCodes).clone() if network_fine is not None else None
 
+    # ---- the sampling schedule of a chunk of R rays, shared by render_rays and render_geometry ---------------------------------------
+    # Its random draws are behaviour: t_rand [R,S] here, u [R,Ni] in _importance_positions (render_rays draws its raw noise between and
+    # after them), each `pytest` draw behind its own np.random.seed(0).
+    def _coarse_positions(self, near, far, R, S, lindisp, perturb, pytest, dev):
+        """The coarse sample positions ``(z, z_stride)`` (render_class.py:266-287).  ``near`` / ``far``: two floats — one row shared by
+        every ray (``z_stride = 0``), built on the host as the reference builds it and cached — or two per-ray ``[R,1]`` columns."""
+        t_row = self._const_row(("t", S), lambda: torch.linspace(0., 1., steps=S), dev)
+        if not torch.is_tensor(near):
+            def z_row():
+                t = torch.linspace(0., 1., steps=S)
+                n, f = torch.tensor([[near]]), torch.tensor([[far]])
+                z = n * (1. - t) + f * t if not lindisp else 1. / (1. / n * (1. - t) + 1. / f * t)
+                return z.reshape(-1)
+
+            z, z_stride = self._const_row(("z", near, far, S, bool(lindisp)), z_row, dev), 0
+        else:
+            z = (near * (1. - t_row) + far * t_row if not lindisp else 1. / (1. / near * (1. - t_row) + 1. / far * t_row)).contiguous()
+            z_stride = S
+        if perturb > 0.:
+            zz = z[None, :].expand(R, S) if z_stride == 0 else z
+            mids = .5 * (zz[..., 1:] + zz[..., :-1])
+            upper, lower = torch.cat([mids, zz[..., -1:]], -1), torch.cat([zz[..., :1], mids], -1)
+            if pytest:
+                np.random.seed(0)
+                t_rand = torch.Tensor(np.random.rand(R, S)).to(dev)
+            else:
+                t_rand = torch.rand(R, S, device=dev)
+            z, z_stride = (lower + (upper - lower) * t_rand).contiguous(), S
+        return z, z_stride
+
+    def _importance_positions(self, z, z_stride, weights, R, S, Ni, perturb, pytest, dev):
+        """``(z_samples [R,Ni], z_fine [R,S+Ni], z_std [R])`` from the coarse pass's weights: ``mofa_sample_pdf_merge``."""
+        if perturb == 0.:            # det=(perturb == 0.), render_class.py:325
+            u, u_stride = self._const_row(("u", Ni), lambda: torch.linspace(0., 1., steps=Ni), dev), 0
+        elif pytest:
+            np.random.seed(0)
+            u, u_stride = torch.Tensor(np.random.rand(R, Ni)).to(dev).contiguous(), Ni
+        else:
+            u, u_stride = torch.rand(R, Ni, device=dev), Ni
+        z_samples = torch.empty(R, Ni, dtype=torch.float32, device=dev)
+        z_fine = torch.empty(R, S + Ni, dtype=torch.float32, device=dev)
+        z_std = torch.empty(R, dtype=torch.float32, device=dev)
+        # z_samples are detached in the reference (render_class.py:326): no gradient through the resampling
+        lib.check(self._lib().mofa_sample_pdf_merge(lib.ptr(z), z_stride, lib.ptr(weights.detach()), lib.ptr(u), u_stride, R, S, Ni,
+                                                    lib.ptr(z_samples), lib.ptr(z_fine), lib.ptr(z_std), lib.stream()), "mofa_sample_pdf_merge")
+        return z_samples, z_fine, z_std
+
+    def _culled_pass(self, occupancy, which, rays_o, rays_d, zv, zs, n_s):
+        """Classify and compact one pass's samples (``occupancy.CulledPass``: one host read, the kept count) and add them to
+        ``self.occupancy_stats[which]``."""
+        from .occupancy import CulledPass
+        cp = CulledPass(occupancy, rays_o, rays_d, zv, zs, n_s)
+        stats = self.occupancy_stats.setdefault(which, {"samples": 0, "kept": 0})
+        stats["samples"] += cp.n_samples
+        stats["kept"] += cp.n_kept
+        return cp
+
+    @staticmethod
+    def _bounds(near, far, rays_d):
+        """``near`` / ``far``, each a scalar (the shipped call sites) or a per-ray array, as render_class.py:174 broadcasts it: two floats
+        (the scalar fast path), or — when either is per ray — two ``[R,1]`` columns beside ``rays_d [R,3]``."""
+        per_ray = lambda v: torch.is_tensor(v) and v.numel() > 1 or isinstance(v, np.ndarray) and v.size > 1
+        if not per_ray(near) and not per_ray(far):
+            return _scalar(near), _scalar(far)
+        ones = torch.ones_like(rays_d[..., :1])
+        return tuple(torch.as_tensor(v, dtype=torch.float32).reshape(-1, 1).to(ones.device) * ones if per_ray(v) else _scalar(v) * ones
+                     for v in (near, far))
+
     # ------------------------------------------------------------------------------------------------
     def render_rays(self, ray_batch, network_fn, N_samples, retraw=False, lindisp=False, perturb=0., N_importance=0,
                     network_fine=None, white_bkgd=False, raw_noise_std=0., network_query_fn=None, verbose=False,
@@ -356,33 +421,8 @@ class Renderer(torch.nn.Module):
         #  drops the scalar fast path: the columns are what the reference's render_rays reads, models/render_class.py:262-264)
         scalar_bounds = (getattr(self, "_rays_ref", None) is self.rays and self._near is not None
                          and self.rays._version == getattr(self, "_rays_version", -1))
-        t_row = self._const_row(("t", S), lambda: torch.linspace(0., 1., steps=S), dev)
-        if scalar_bounds:
-            near, far = self._near, self._far
-
-            def z_row():
-                t = torch.linspace(0., 1., steps=S)
-                n, f = torch.tensor([[near]]), torch.tensor([[far]])
-                z = n * (1. - t) + f * t if not lindisp else 1. / (1. / n * (1. - t) + 1. / f * t)
-                return z.reshape(-1)
-
-            z = self._const_row(("z", near, far, S, bool(lindisp)), z_row, dev)
-            z_stride = 0
-        else:
-            n, f = rays[:, 6:7], rays[:, 7:8]
-            z = (n * (1. - t_row) + f * t_row if not lindisp else 1. / (1. / n * (1. - t_row) + 1. / f * t_row)).contiguous()
-            z_stride = S
-        if perturb > 0.:
-            zz = z[None, :].expand(R, S) if z_stride == 0 else z
-            mids = .5 * (zz[..., 1:] + zz[..., :-1])
-            upper, lower = torch.cat([mids, zz[..., -1:]], -1), torch.cat([zz[..., :1], mids], -1)
-            if pytest:
-                np.random.seed(0)
-                t_rand = torch.Tensor(np.random.rand(R, S)).to(dev)
-            else:
-                t_rand = torch.rand(R, S, device=dev)
-            z = (lower + (upper - lower) * t_rand).contiguous()
-            z_stride = S
+        near, far = (self._near, self._far) if scalar_bounds else (rays[:, 6:7], rays[:, 7:8])
+        z, z_stride = self._coarse_positions(near, far, R, S, lindisp, perturb, pytest, dev)
 
         def noise_for(n_s):
             if not raw_noise_std > 0.:
@@ -450,12 +490,8 @@ class Renderer(torch.nn.Module):
         def network_culled(net, folded, zv, zs, n_s, which):
             # classify, compact (one host read: n_kept), network on the kept samples as explicit points with one view direction each
             # (S = 1), scatter: every element of raw is written by the scatter kernel
-            from .occupancy import CulledPass
             h = self._hip(net)
-            cp = CulledPass(occupancy, rays_o, rays_d, zv, zs, n_s)
-            stats = self.occupancy_stats.setdefault(which, {"samples": 0, "kept": 0})
-            stats["samples"] += cp.n_samples
-            stats["kept"] += cp.n_kept
+            cp = self._culled_pass(occupancy, which, rays_o, rays_d, zv, zs, n_s)
             raw = torch.empty(R, n_s, 4, dtype=torch.float32, device=dev)
             raw_kept = None
             if cp.n_kept:
@@ -481,20 +517,7 @@ class Renderer(torch.nn.Module):
 
         if N_importance > 0 and self.is_run_fineNet:
             Ni = int(N_importance)
-            if perturb == 0.:            # det=(perturb == 0.), render_class.py:325
-                u, u_stride = self._const_row(("u", Ni), lambda: torch.linspace(0., 1., steps=Ni), dev), 0
-            elif pytest:
-                np.random.seed(0)
-                u, u_stride = torch.Tensor(np.random.rand(R, Ni)).to(dev).contiguous(), Ni
-            else:
-                u, u_stride = torch.rand(R, Ni, device=dev), Ni
-            z_samples = torch.empty(R, Ni, dtype=torch.float32, device=dev)
-            z_fine = torch.empty(R, S + Ni, dtype=torch.float32, device=dev)
-            z_std = torch.empty(R, dtype=torch.float32, device=dev)
-            # z_samples are detached in the reference (render_class.py:326): no gradient through the resampling
-            lib.check(L.mofa_sample_pdf_merge(lib.ptr(z), z_stride, lib.ptr(c["weights"].detach()), lib.ptr(u), u_stride, R, S,
-                                              Ni, lib.ptr(z_samples), lib.ptr(z_fine), lib.ptr(z_std), st),
-                      "mofa_sample_pdf_merge")
+            z_samples, z_fine, z_std = self._importance_positions(z, z_stride, c["weights"], R, S, Ni, perturb, pytest, dev)
             fine = network_fn if network_fine is None else network_fine
             folded = self._folded_coarse if network_fine is None else self._folded_fine
             raw = (network(fine, folded, z_fine, S + Ni, S + Ni) if occupancy is None else
@@ -523,14 +546,16 @@ class Renderer(torch.nn.Module):
             raise lib.MofaError(f"raw_noise_std = {raw_noise_std} with occupancy: noise would give the skipped samples a density; "
                                 "culled rendering is for inference (raw_noise_std = 0)")
         if torch.is_grad_enabled():
-            rg = lambda t: torch.is_tensor(t) and t.requires_grad
             nets = [unwrap(n) for n in (network_fn, network_fine) if n is not None]
-            asks = (rg(rays) or rg(self.shapeCodes) or rg(self.decoding_texCodes) or rg(self.expCodes_Sigma[self.expType]) or
-                    any(q.requires_grad for q in unwrap(self.idSpecificMod).parameters()) or
-                    (self._weight_grads and any(q.requires_grad for n in nets for q in n.parameters())))
-            if asks:
+            if self._asks_grad(rays) or (self._weight_grads and any(q.requires_grad for n in nets for q in n.parameters())):
                 raise lib.MofaError("occupancy: culled rendering is inference only, but autograd is enabled and a tensor (rays, codes, "
                                     "StyleModule or network weights) asks for a gradient; render under torch.no_grad()")
+
+    def _asks_grad(self, *tensors):
+        """Whether one of ``tensors``, of this call's codes or of the StyleModule's parameters asks for a gradient."""
+        rg = lambda t: torch.is_tensor(t) and t.requires_grad
+        return (any(rg(t) for t in tensors) or rg(self.shapeCodes) or rg(self.decoding_texCodes) or rg(self.expCodes_Sigma[self.expType]) or
+                any(q.requires_grad for q in unwrap(self.idSpecificMod).parameters()))
 
     # ------------------------------------------------------------------------------------------------
     def _make_rays(self, H, W, K, c2w, rays, use_viewdirs, c2w_staticcam, ndc):
@@ -573,18 +598,13 @@ class Renderer(torch.nn.Module):
         kwargs = dict(kwargs)
         kwargs.pop("network_query_fn", None)
         rays_o, rays_d, viewdirs, sh = self._make_rays(H, W, K, c2w, rays, use_viewdirs, c2w_staticcam, ndc)
-        ones = torch.ones_like(rays_d[..., :1])
-
-        def bound(v):      # scalar (the shipped call sites) or a per-ray array, as render_class.py:174 broadcasts it
-            if torch.is_tensor(v) and v.numel() > 1 or isinstance(v, np.ndarray) and v.size > 1:
-                return None, torch.as_tensor(v, dtype=torch.float32).reshape(-1, 1).to(ones.device) * ones
-            return _scalar(v), _scalar(v) * ones
-
-        self._near, ncol = bound(near)
-        self._far, fcol = bound(far)
-        if self._near is None or self._far is None:
+        near, far = self._bounds(near, far, rays_d)
+        if torch.is_tensor(near):       # per ray: render_rays reads them from columns 6:8
             self._near = self._far = None
-        self.rays = torch.cat([rays_o, rays_d, ncol, fcol, viewdirs], -1)
+        else:
+            ones = torch.ones_like(rays_d[..., :1])
+            self._near, self._far, near, far = near, far, near * ones, far * ones
+        self.rays = torch.cat([rays_o, rays_d, near, far, viewdirs], -1)
         self._rays_ref = self.rays          # (a reference, not an id: ids are reused after garbage collection)
         self._rays_version = self.rays._version
         self.decoding_texCodes = tex_code
@@ -694,6 +714,25 @@ class Renderer(torch.nn.Module):
             else:
                 self.expCodes_Sigma[20] = expCodes
 
+    def _fold_density(self, network, dev):
+        """The folded codes of a density query.  The texture code feeds only the uv layers, which a density query does not run: zeros
+        fold as well as any code."""
+        return self._fold_codes(network, torch.zeros(self._hip(network).ch_tex, dtype=torch.float32, device=dev)).clone()
+
+    def _density_setup(self, what, network, shapeCodes, expType, expCodes, netchunk):
+        """What ``query_density`` and ``extract_mesh``'s narrow band (``what``: the name in the error texts) do before their first launch:
+        the chunk, the codes on ``self``, the network's device, the folded codes -> ``(HipNet, device, chunk, folded)``."""
+        chunk = int(netchunk if netchunk is not None else self.netchunk)
+        if chunk < 1:
+            raise lib.MofaError(f"{what}: netchunk = {chunk}")
+        self._set_codes(shapeCodes, expType, expCodes)
+        h = self._hip(network)
+        dev = next(unwrap(network).parameters()).device
+        if dev.type != "cuda":
+            raise lib.MofaError(f"{what}: the network must live on the GPU (net.cuda()); there is no CPU path")
+        with torch.no_grad():
+            return h, dev, chunk, self._fold_density(network, dev)
+
     def query_density(self, network, pts=None, *, bounds=None, resolution=None, shapeCodes, expType=20, expCodes=None, netchunk=None):
         """The network's density — the pre-ReLU ``raw[..., 3]`` of ``run_network``, bit for bit — at explicit points ``pts [N,3]``
         (returns ``[N]``) or on the grid ``bounds = ((x0,y0,z0), (x1,y1,z1))`` x ``resolution = (nx,ny,nz)`` (returns ``[nx,ny,nz]``, sample
@@ -705,17 +744,8 @@ class Renderer(torch.nn.Module):
         from . import mesh
         if (pts is None) == (bounds is None or resolution is None):
             raise lib.MofaError("query_density: give pts, or bounds and resolution")
-        chunk = int(netchunk if netchunk is not None else self.netchunk)
-        if chunk < 1:
-            raise lib.MofaError(f"query_density: netchunk = {chunk}")
-        self._set_codes(shapeCodes, expType, expCodes)
-        h = self._hip(network)
-        dev = next(unwrap(network).parameters()).device
-        if dev.type != "cuda":
-            raise lib.MofaError("query_density: the network must live on the GPU (net.cuda()); there is no CPU path")
+        h, dev, chunk, folded = self._density_setup("query_density", network, shapeCodes, expType, expCodes, netchunk)
         with torch.no_grad():
-            # the texture code feeds only the uv layers, which a density query does not run: zeros fold as well as any code
-            folded = self._fold_codes(network, torch.zeros(h.ch_tex, dtype=torch.float32, device=dev)).clone()
             if pts is not None:
                 if not torch.is_tensor(pts) or pts.dim() != 2 or pts.shape[-1] != 3:
                     raise lib.MofaError(f"query_density: pts must be a [N,3] tensor, got {getattr(pts, 'shape', type(pts))}")
@@ -810,13 +840,7 @@ class Renderer(torch.nn.Module):
                 raise lib.MofaError("render_geometry: the rays are CPU tensors; there is no CPU path")
             rays_o, rays_d, viewdirs = (t.detach().float().contiguous() for t in (rays_o, rays_d, viewdirs))
             dev, n_rays = rays_o.device, int(rays_o.shape[0])
-            per_ray = lambda v: torch.is_tensor(v) and v.numel() > 1 or isinstance(v, np.ndarray) and v.size > 1
-            col = lambda v: torch.as_tensor(v, dtype=torch.float32).detach().reshape(-1, 1).to(dev) * torch.ones_like(rays_d[..., :1])
-            scalar_bounds = not per_ray(near) and not per_ray(far)
-            if scalar_bounds:       # one shared row of sample positions, built on the host as render_rays builds it
-                near, far = _scalar(near), _scalar(far)
-            else:
-                ncol, fcol = (col(v) if per_ray(v) else _scalar(v) * torch.ones_like(rays_d[..., :1]) for v in (near, far))
+            near, far = self._bounds(near, far, rays_d)
             self._set_codes(shapeCodes, expType, expCodes)
             self.occupancy_stats = None
             if occupancy is not None:
@@ -825,36 +849,14 @@ class Renderer(torch.nn.Module):
             fine_pass = Ni > 0 and self.is_run_fineNet
             fine = network_fn if network_fine is None else network_fine
             nets = [network_fn] + ([fine] if fine_pass and fine is not network_fn else [])
-            # the texture code feeds only the uv layers, which a density query does not run: zeros fold as well as any code
-            folded = {id(n): self._fold_codes(n, torch.zeros(self._hip(n).ch_tex, dtype=torch.float32, device=dev)).clone() for n in nets}
+            folded = {id(n): self._fold_density(n, dev) for n in nets}
             st = lib.stream()
             out: Dict[str, list] = {}
             for b0 in range(0, n_rays, int(chunk)):
                 ro, rd, vd = rays_o[b0:b0 + chunk], rays_d[b0:b0 + chunk], viewdirs[b0:b0 + chunk]
                 R = int(ro.shape[0])
-                t_row = self._const_row(("t", S), lambda: torch.linspace(0., 1., steps=S), dev)
-                if scalar_bounds:
-                    def z_row():
-                        t = torch.linspace(0., 1., steps=S)
-                        n, f = torch.tensor([[near]]), torch.tensor([[far]])
-                        z = n * (1. - t) + f * t if not lindisp else 1. / (1. / n * (1. - t) + 1. / f * t)
-                        return z.reshape(-1)
-
-                    z, z_stride = self._const_row(("z", near, far, S, lindisp), z_row, dev), 0
-                else:
-                    n, f = ncol[b0:b0 + chunk], fcol[b0:b0 + chunk]
-                    z = (n * (1. - t_row) + f * t_row if not lindisp else 1. / (1. / n * (1. - t_row) + 1. / f * t_row)).contiguous()
-                    z_stride = S
-                if perturb > 0.:
-                    zz = z[None, :].expand(R, S) if z_stride == 0 else z
-                    mids = .5 * (zz[..., 1:] + zz[..., :-1])
-                    upper, lower = torch.cat([mids, zz[..., -1:]], -1), torch.cat([zz[..., :1], mids], -1)
-                    if pytest:
-                        np.random.seed(0)
-                        t_rand = torch.Tensor(np.random.rand(R, S)).to(dev)
-                    else:
-                        t_rand = torch.rand(R, S, device=dev)
-                    z, z_stride = (lower + (upper - lower) * t_rand).contiguous(), S
+                bounds = (near[b0:b0 + chunk], far[b0:b0 + chunk]) if torch.is_tensor(near) else (near, far)
+                z, z_stride = self._coarse_positions(*bounds, R, S, lindisp, perturb, pytest, dev)
 
                 def one_pass(net, zv, zs, n_s, which):
                     h, fold = self._hip(net), folded[id(net)]
@@ -869,11 +871,7 @@ class Renderer(torch.nn.Module):
                                                         lib.ptr(pts[:m]), st), "mofa_ray_points")
                             h.density_points(pts[:m], sigma[i:j].reshape(-1), fold)
                     else:      # classify, compact (one host read: n_kept), density of the kept points, scatter (writes every element)
-                        from .occupancy import CulledPass
-                        cp = CulledPass(occupancy, ro, rd, zv, zs, n_s)
-                        stats = self.occupancy_stats.setdefault(which, {"samples": 0, "kept": 0})
-                        stats["samples"] += cp.n_samples
-                        stats["kept"] += cp.n_kept
+                        cp = self._culled_pass(occupancy, which, ro, rd, zv, zs, n_s)
                         kept = None
                         if cp.n_kept:
                             pts, _, _ = cp.gather(vd)
@@ -893,18 +891,7 @@ class Renderer(torch.nn.Module):
                 z_last, w_last = (z if z_stride else z[None, :].expand(R, S)), c["weights"]
                 z_med, zs_med = z, z_stride
                 if fine_pass:
-                    if perturb == 0.:
-                        u, u_stride = self._const_row(("u", Ni), lambda: torch.linspace(0., 1., steps=Ni), dev), 0
-                    elif pytest:
-                        np.random.seed(0)
-                        u, u_stride = torch.Tensor(np.random.rand(R, Ni)).to(dev).contiguous(), Ni
-                    else:
-                        u, u_stride = torch.rand(R, Ni, device=dev), Ni
-                    z_samples = torch.empty(R, Ni, dtype=torch.float32, device=dev)
-                    z_fine = torch.empty(R, S + Ni, dtype=torch.float32, device=dev)
-                    z_std = torch.empty(R, dtype=torch.float32, device=dev)
-                    lib.check(L.mofa_sample_pdf_merge(lib.ptr(z), z_stride, lib.ptr(c["weights"]), lib.ptr(u), u_stride, R, S, Ni,
-                                                      lib.ptr(z_samples), lib.ptr(z_fine), lib.ptr(z_std), st), "mofa_sample_pdf_merge")
+                    _, z_fine, z_std = self._importance_positions(z, z_stride, c["weights"], R, S, Ni, perturb, pytest, dev)
                     f = one_pass(fine, z_fine, S + Ni, S + Ni, "fine")
                     ret = {"depth": f["depth"], "disp": f["disp"], "acc": f["acc"], "depth0": c["depth"], "disp0": c["disp"],
                            "acc0": c["acc"], "z_std": z_std}
@@ -973,13 +960,37 @@ class Renderer(torch.nn.Module):
         def row(v, i):
             return v[i].reshape(1, -1) if torch.is_tensor(v) and v.dim() == 2 and v.shape[0] == n_poses and n_poses > 1 else v
 
+        def frame(i, paths, sink):
+            et = 20 if expType is None else (expType[i] if hasattr(expType, "__len__") else expType)
+            depth, disp, acc, ex = self.render_geometry(height, width, K, chunk=chunk, c2w=render_poses[i][:3, :4], ndc=ndc, near=near, far=far,
+                                                        shapeCodes=row(shapeCodes, i), expType=et, expCodes=row(expCodes, i),
+                                                        normals=True, **surface, **kw)
+            surf = ex["depth_median"] if which == "median" else depth
+            if paths is not None:
+                valid = ex["normals_valid"].to(torch.float32)[..., None]
+                grey = lambda t: t[..., None].expand(*t.shape, 3)
+                span = torch.full_like(surf, far - near)          # a tensor divisor: an elementwise, correctly rounded division
+                check = self.frame_check()                       # one snapshot of this frame's verdicts for its three files
+                for f, img in zip(paths, (valid * ((ex["normals"] + 1.) / 2.), grey((acc >= _scalar(acc_min)).to(torch.float32)),
+                                          grey((surf - near) / span))):
+                    sink.submit(f, img, check=check)
+            return dict(ex, depth=depth, disp=disp, acc=acc, depth_surface=surf)
+
+        out = self._pose_loop(n_poses, name, savedir, ("_normals.png", "_mask.png", "_depth.png"), frame)
+        self.check_launches(block=True)
+        return out
+
+    def _pose_loop(self, n_poses, name, savedir, tails, frame):
+        """The loop of :meth:`render_path_geometry` and :meth:`render_path_mesh`: for each pose number ``i``, ``frame(i, paths, sink)``
+        -> a dict of tensors, where ``paths`` are the pose's files ``<savedir>/<stem><tail>`` (``None`` without ``savedir``; ``stem`` is the
+        pose's number, or ``name``, followed by the number when there are several poses) and ``sink`` the ``PngSink`` to submit them to
+        (``self.png_sink``, or one of the loop's own, closed at its end).  A pose whose files all exist is skipped, so a bulk render can
+        resume.  Returns the dicts stacked over the rendered poses as numpy arrays, with ``rendered`` and ``skipped``, the lists of pose
+        numbers."""
         def stem(i):
             if name is None:
                 return "{:03d}".format(i)
             return str(name) if n_poses == 1 else "{}_{:03d}".format(name, i)
-
-        def files(i):
-            return [os.path.join(savedir, stem(i) + tail) for tail in ("_normals.png", "_mask.png", "_depth.png")]
 
         from .io import PngSink
         frames: Dict[str, list] = {}
@@ -987,33 +998,20 @@ class Renderer(torch.nn.Module):
         shared = self.png_sink
         sink = shared if shared is not None else PngSink()
         try:
-            for i, pose in enumerate(render_poses):
-                paths = files(i) if savedir is not None else None
+            for i in range(n_poses):
+                paths = [os.path.join(savedir, stem(i) + tail) for tail in tails] if savedir is not None else None
                 if paths is not None and all(os.path.exists(f) for f in paths):
-                    skipped.append(i)                       # bulk renders resume by skipping finished poses
+                    skipped.append(i)
                     continue
-                et = 20 if expType is None else (expType[i] if hasattr(expType, "__len__") else expType)
-                depth, disp, acc, ex = self.render_geometry(height, width, K, chunk=chunk, c2w=pose[:3, :4], ndc=ndc, near=near, far=far,
-                                                            shapeCodes=row(shapeCodes, i), expType=et, expCodes=row(expCodes, i),
-                                                            normals=True, **surface, **kw)
-                surf = ex["depth_median"] if which == "median" else depth
-                if paths is not None:
-                    valid = ex["normals_valid"].to(torch.float32)[..., None]
-                    grey = lambda t: t[..., None].expand(*t.shape, 3)
-                    span = torch.full_like(surf, far - near)          # a tensor divisor: an elementwise, correctly rounded division
-                    check = self.frame_check()                       # one snapshot of this frame's verdicts for its three files
-                    for f, img in zip(paths, (valid * ((ex["normals"] + 1.) / 2.), grey((acc >= _scalar(acc_min)).to(torch.float32)),
-                                              grey((surf - near) / span))):
-                        sink.submit(f, img, check=check)
+                tensors = frame(i, paths, sink)
                 rendered.append(i)
-                for k, v in dict(ex, depth=depth, disp=disp, acc=acc, depth_surface=surf).items():
+                for k, v in tensors.items():
                     frames.setdefault(k, []).append(v.detach())
         finally:
             if shared is None:
                 sink.close()
         out = {k: torch.stack(v, 0).cpu().numpy() for k, v in frames.items()}
         out["rendered"], out["skipped"] = rendered, skipped
-        self.check_launches(block=True)
         return out
 
     def render_mesh(self, H, W, K, c2w, verts, faces, colors=None, znear=1e-3, ambient=0.3):
@@ -1053,46 +1051,25 @@ class Renderer(torch.nn.Module):
         rendered poses — ``rgb``, ``depth``, ``mask``, ``face`` — with ``rendered`` and ``skipped``, the lists of pose numbers."""
         height, width, _ = hwf
         height, width = int(height), int(width)
-        n_poses = len(render_poses)
         if (near is None) != (far is None) or (near is not None and not _scalar(far) > _scalar(near)):
             raise lib.MofaError(f"render_path_mesh: near = {near}, far = {far} (want both or neither, far > near)")
 
-        def stem(i):
-            if name is None:
-                return "{:03d}".format(i)
-            return str(name) if n_poses == 1 else "{}_{:03d}".format(name, i)
+        def frame(i, paths, sink):
+            rgb, depth, mask, ex = self.render_mesh(height, width, K, render_poses[i][:3, :4], verts, faces, colors=colors, znear=znear,
+                                                    ambient=ambient)
+            if paths is not None:
+                if near is None:
+                    hit = depth[mask]
+                    lo, hi = (hit.min(), hit.max()) if hit.numel() else (depth.new_zeros(()), depth.new_ones(()))
+                    span = torch.where(hi > lo, hi - lo, torch.ones_like(hi))
+                else:
+                    lo, span = depth.new_tensor(_scalar(near)), depth.new_tensor(_scalar(far) - _scalar(near))
+                grey = ((depth - lo) / span) * mask.to(torch.float32)
+                sink.submit(paths[0], rgb)
+                sink.submit(paths[1], grey[..., None].expand(height, width, 3))
+            return {"rgb": rgb, "depth": depth, "mask": mask, "face": ex["face"]}
 
-        from .io import PngSink
-        frames: Dict[str, list] = {}
-        rendered, skipped = [], []
-        shared = self.png_sink
-        sink = shared if shared is not None else PngSink()
-        try:
-            for i, pose in enumerate(render_poses):
-                paths = [os.path.join(savedir, stem(i) + tail) for tail in ("_mesh.png", "_mesh_depth.png")] if savedir is not None else None
-                if paths is not None and all(os.path.exists(f) for f in paths):
-                    skipped.append(i)
-                    continue
-                rgb, depth, mask, ex = self.render_mesh(height, width, K, pose[:3, :4], verts, faces, colors=colors, znear=znear, ambient=ambient)
-                if paths is not None:
-                    if near is None:
-                        hit = depth[mask]
-                        lo, hi = (hit.min(), hit.max()) if hit.numel() else (depth.new_zeros(()), depth.new_ones(()))
-                        span = torch.where(hi > lo, hi - lo, torch.ones_like(hi))
-                    else:
-                        lo, span = depth.new_tensor(_scalar(near)), depth.new_tensor(_scalar(far) - _scalar(near))
-                    grey = ((depth - lo) / span) * mask.to(torch.float32)
-                    sink.submit(paths[0], rgb)
-                    sink.submit(paths[1], grey[..., None].expand(height, width, 3))
-                rendered.append(i)
-                for k, v in (("rgb", rgb), ("depth", depth), ("mask", mask), ("face", ex["face"])):
-                    frames.setdefault(k, []).append(v.detach())
-        finally:
-            if shared is None:
-                sink.close()
-        out = {k: torch.stack(v, 0).cpu().numpy() for k, v in frames.items()}
-        out["rendered"], out["skipped"] = rendered, skipped
-        return out
+        return self._pose_loop(len(render_poses), name, savedir, ("_mesh.png", "_mesh_depth.png"), frame)
 
     def build_occupancy(self, networks, *, bounds, resolution, threshold, shapeCodes, expType=20, expCodes=None, dilate=1, netchunk=None):
         """Occupancy grid for ``render_rays(..., occupancy=...)``: the density of each of ``networks`` (one network or a sequence,
@@ -1163,15 +1140,7 @@ class Renderer(torch.nn.Module):
     def _band_mesh(self, network, res, lo, step, level, brick, shapeCodes, expType, expCodes, netchunk):
         """extract_mesh's narrow-band path: mesh.band_surface over HipNet.density_points; the statistics go to self.mesh_stats."""
         from . import mesh
-        chunk = int(netchunk if netchunk is not None else self.netchunk)
-        if chunk < 1:
-            raise lib.MofaError(f"extract_mesh: netchunk = {chunk}")
-        self._set_codes(shapeCodes, expType, expCodes)
-        h = self._hip(network)
-        dev = next(unwrap(network).parameters()).device
-        if dev.type != "cuda":
-            raise lib.MofaError("extract_mesh: the network must live on the GPU (net.cuda()); there is no CPU path")
-        folded = self._fold_codes(network, torch.zeros(h.ch_tex, dtype=torch.float32, device=dev)).clone()
+        h, _, chunk, folded = self._density_setup("extract_mesh", network, shapeCodes, expType, expCodes, netchunk)
 
         def density(pts):
             out = torch.empty(pts.shape[0], dtype=torch.float32, device=pts.device)

@@ -207,6 +207,7 @@ def codes(seed=0):
 def full_frame(render, kw, K, ro, rd, H=16, chunk=4096, tex=None, **more):
     """render_fitting: (rgb, disp, acc, extras)."""
     bm, t, exp = codes()
+    torch.manual_seed(11)                                             # the device_rng case: both renders draw from the same generator state
     with torch.no_grad():
         out = render.render_fitting(H, H, K, chunk=chunk, rays=torch.stack([ro, rd], 0), shapeCodes=bm, uvCodes=t if tex is None else tex,
                                     expType=20, expCodes=exp, **dict(kw, **more))
@@ -217,6 +218,7 @@ def full_frame(render, kw, K, ro, rd, H=16, chunk=4096, tex=None, **more):
 def geometry(render, kw, K, ro, rd, H=16, chunk=4096, bm=None, exp=None, **more):
     """render_geometry: (depth, disp, acc, extras)."""
     b, _, e = codes()
+    torch.manual_seed(11)
     out = render.render_geometry(H, H, K, chunk=chunk, rays=torch.stack([ro, rd], 0), shapeCodes=b if bm is None else bm, expType=20,
                                  expCodes=e if exp is None else exp, **dict(kw, **more))
     render.check_launches(block=True)
@@ -227,8 +229,10 @@ def same_frames(a, b):
     return (all(same(x, y) for x, y in zip(a[:3], b[:3])) and set(a[3]) == set(b[3]) and all(same(a[3][k], b[3][k]) for k in a[3]))
 
 
+# device_rng: the draws come from torch.rand on the device, so only the ORDER and SHAPES of the two renders' draws (t_rand [R,S], then
+# u [R,Ni]) hold the frames together
 _cases = {"det": dict(perturb=0.), "stochastic": dict(perturb=1., pytest=True), "lindisp": dict(lindisp=True), "per_ray_bounds": "bounds",
-          "coarse_only": dict()}
+          "coarse_only": dict(), "device_rng": dict(perturb=1.)}
 
 
 @pytest.mark.parametrize("case", list(_cases))
