@@ -237,6 +237,9 @@ size_t train_partial_floats(int64_t m_padded, int n_padded, int k_padded) {
 size_t train_wws_floats(const Plan& p, int D, int64_t n_points) {
     const int64_t mp = round_up(n_points, kRowTile);
     size_t n = mofa_weight_grad_workspace_floats(n_points, p.Wp, p.Wp);
+    // layer 0 contracts the encoding (pe_k columns): wider than Wp for a network of width <= 64 behind more than ten frequencies
+    const size_t first = mofa_weight_grad_workspace_floats(n_points, p.Wp, p.pe_k);
+    if (first > n) n = first;
     if (train_chain_shape(p, D)) {
         const size_t chain = (size_t)(D + 4) * train_partial_floats(mp, p.Wp, p.Wp);
         if (chain > n) n = chain;
