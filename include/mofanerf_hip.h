@@ -269,6 +269,49 @@ int mofa_band_emit(int64_t nx, int64_t ny, int64_t nz, int32_t brick, const floa
                    const void* workspace, int64_t n_active, const void* mesh_workspace, float* verts, int64_t* edge_ids, int32_t* faces,
                    void* stream);
 
+/* Vertex refinement: every vertex of mofa_iso_emit / mofa_band_emit keeps its lattice edge and moves along it by a bracketed bisection on
+ * the density itself, and density normals come from central differences.  The kernels make sample points and consume densities; the
+ * caller evaluates the density in between (a point evaluated twice must give the same bits, as for the narrow band).  Faces, vertex
+ * numbering and topology are untouched.  Plain fp32, every operation rounded separately; no atomics but the error counters
+ * counts[MOFA_REFINE_COUNTS] (int64, DEVICE), which the CALLER zeroes and the kernels add to, so the same input gives the same bits.
+ *   mofa_iso_edge_ids        after mofa_iso_count on the same workspace: edge_ids[V] (int64) = the edge_id of every vertex in
+ *                            mofa_iso_emit's order (mofa_band_emit returns its own).  Writes nothing when V or F exceeds 2^31 - 1.
+ *   mofa_edge_points         pts[n,3] for the vertices first .. first+n-1 (edge_ids, t_lo, t_hi are indexed by vertex, pts by vertex - first):
+ *                            mode 0 the edge's lower end p_a, mode 1 its upper end p_b (both the bits of mofa_grid_points), mode 2 the
+ *                            bracket's midpoint p_a + t_m (p_b - p_a), t_m = 0.5 (t_lo + t_hi) (exact for 23 halvings).  t_lo / t_hi may
+ *                            be NULL for modes 0 and 1.  An edge id outside [0, 7 nx ny nz) or an edge that leaves the grid adds one to
+ *                            counts[MOFA_REFINE_REFUSED] and its point is not written.
+ *   mofa_edge_bracket_init   t_lo = 0, t_hi = 1, s_lo = s_a, s_hi = s_b (the densities at p_a, p_b); counts[MOFA_REFINE_NO_STRADDLE] +=
+ *                            edges whose ends lie on one side of the level (inside(s) = s >= level, NaN outside),
+ *                            counts[MOFA_REFINE_NON_FINITE] += non-finite values.
+ *   mofa_edge_bracket_update s_m = the densities at the midpoints: inside(s_m) == inside(s_lo) ? (t_lo, s_lo) = (t_m, s_m) :
+ *                            (t_hi, s_hi) = (t_m, s_m).  A non-finite s_m adds one to counts[MOFA_REFINE_NON_FINITE] and leaves its bracket.
+ *   mofa_edge_place          u = (level - s_lo) / (s_hi - s_lo), t = t_lo + u (t_hi - t_lo), verts[v] = p_a + t (p_b - p_a).  With an
+ *                            untouched bracket t = u: mofa_iso_emit's vertex, bit for bit.  Refused edges as for mofa_edge_points.
+ *   mofa_fd_points           pts[6n,3] for the vertices first .. first+n-1 of verts: v + h_x e_x, v - h_x e_x, then y, then z.
+ *   mofa_fd_normals          s[6n] = the densities at those points: g_a = (s_+ - s_-) / (2 h_a) in fp32, normals[v] = -g / |g| with the norm
+ *                            and the division in fp64 from the three fp32 components, rounded once (toward lower density, like the face
+ *                            normals).  A zero or non-finite g gives (0, 0, 0) and adds one to counts[MOFA_REFINE_ZERO_NORMAL].
+ * The lattice needs 2 <= n < 2^24 per axis and fewer than 2^48 samples; lo / step / h: HOST arrays (finite, step > 0, h > 0); the level
+ * must be finite; 1 <= n <= (2^31 - 1) 256 elements per call. */
+#define MOFA_REFINE_NO_STRADDLE 0
+#define MOFA_REFINE_NON_FINITE 1
+#define MOFA_REFINE_REFUSED 2
+#define MOFA_REFINE_ZERO_NORMAL 3
+#define MOFA_REFINE_COUNTS 4
+int mofa_iso_edge_ids(int64_t nx, int64_t ny, int64_t nz, const void* workspace, int64_t* edge_ids, void* stream);
+int mofa_edge_points(int64_t nx, int64_t ny, int64_t nz, const float lo[3], const float step[3], const int64_t* edge_ids, const float* t_lo,
+                     const float* t_hi, int64_t first, int64_t n, int32_t mode, float* pts, int64_t* counts, void* stream);
+int mofa_edge_bracket_init(const float* s_a, const float* s_b, float level, int64_t n, float* t_lo, float* t_hi, float* s_lo, float* s_hi,
+                           int64_t* counts, void* stream);
+int mofa_edge_bracket_update(const float* s_m, float level, int64_t n, float* t_lo, float* t_hi, float* s_lo, float* s_hi, int64_t* counts,
+                             void* stream);
+int mofa_edge_place(int64_t nx, int64_t ny, int64_t nz, const float lo[3], const float step[3], const int64_t* edge_ids, const float* t_lo,
+                    const float* t_hi, const float* s_lo, const float* s_hi, float level, int64_t n, float* verts, int64_t* counts,
+                    void* stream);
+int mofa_fd_points(const float* verts, const float h[3], int64_t first, int64_t n, float* pts, void* stream);
+int mofa_fd_normals(const float* s, const float h[3], int64_t n, float* normals, int64_t* counts, void* stream);
+
 /* ---- occupancy-culled rendering: skip the network where an occupancy grid says the space is empty ---------------------------------
  * The grid lives on the lattice of mofa_grid_points (nx x ny x nz samples at lo + (i,j,k) step): (nx-1)(ny-1)(nz-1) cells, one byte
  * each (0 / 1), cell index (i (ny-1) + j) (nz-1) + k.  The lattice needs 2 <= n < 2^24 per axis and fewer than 2^31 cells.

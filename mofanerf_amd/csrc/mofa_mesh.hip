@@ -9,10 +9,12 @@
 //   vertex          t = (level - s_a) / (s_b - s_a), p = p_a + t (p_b - p_a), every operation separately rounded, a = lower endpoint
 //   order           vertices by edge_id; faces by cell, then tet, then triangle; normals (v1 - v0) x (v2 - v0) point toward lower sigma
 //
-// Kernels: k_iso_edge_flags, k_iso_cell_counts (+ the scans and k_iso_totals: mofa_iso_count), k_iso_vertices, k_iso_faces (mofa_iso_emit).
+// Kernels: k_iso_edge_flags, k_iso_cell_counts (+ the scans and k_iso_totals: mofa_iso_count), k_iso_vertices, k_iso_faces (mofa_iso_emit),
+// k_iso_edge_ids (mofa_iso_edge_ids: each vertex's edge, for the refinement in mofa_refine.hip).
 #include <math.h>
 
 #include "mofa_common.h"
+#include "mofa_lattice.h"
 
 namespace mofa {
 namespace {
@@ -22,15 +24,9 @@ constexpr int kScanTile = 256 * kScanItems;         // elements per workgroup
 constexpr long long kIsoMaxEdges = 1ll << 31;       // 7 nx ny nz must stay below this
 constexpr long long kIsoMaxOut = 2147483647ll;      // V and F must fit int32 face indices
 
-__device__ __forceinline__ float grid_coord(float lo, float step, long long i) { return __fadd_rn(lo, __fmul_rn((float)i, step)); }
-
-__device__ __forceinline__ bool inside(float s, float level) { return s >= level; }     // (false for NaN)
-
+// (grid_coord, inside and the direction tables kDirDx / kDirDy / kDirDz: mofa_lattice.h)
 // offset (dx + 2 dy + 4 dz) of a tet edge -> lattice direction 0..6 (+x, +y, +z, +x+y, +x+z, +y+z, +x+y+z)
 __device__ __constant__ int kDirOfOffset[8] = {-1, 0, 1, 3, 2, 4, 5, 6};
-__device__ __constant__ int kDirDx[7] = {1, 0, 0, 1, 1, 0, 1};
-__device__ __constant__ int kDirDy[7] = {0, 1, 0, 1, 0, 1, 1};
-__device__ __constant__ int kDirDz[7] = {0, 0, 1, 0, 1, 1, 1};
 // the 6 axis permutations (a,b,c) in lexicographic order, and the sign of each (the orientation of its tet)
 __device__ __constant__ int kPerm[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
 __device__ __constant__ int kPermSign[6] = {1, -1, -1, 1, 1, -1};
@@ -210,6 +206,16 @@ __global__ __launch_bounds__(256) void k_iso_vertices(const float* __restrict__ 
     for (int a = 0; a < 3; ++a) verts[v * 3 + a] = __fadd_rn(pa[a], __fmul_rn(t, __fsub_rn(pb[a], pa[a])));
 }
 
+// edge_ids[v] = the edge of vertex v: the flagged edges compacted through their scan (k_iso_vertices' numbering)
+__global__ __launch_bounds__(256) void k_iso_edge_ids(long long n_edges, const unsigned char* __restrict__ flags,
+                                                      const long long* __restrict__ escan, const long long* __restrict__ totals,
+                                                      int64_t* __restrict__ edge_ids) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_edges || !flags[e]) return;
+    if (totals[0] > kIsoMaxOut || totals[1] > kIsoMaxOut) return;
+    edge_ids[escan[e]] = e;
+}
+
 __global__ __launch_bounds__(256) void k_iso_faces(const float* __restrict__ grid, long long nx, long long ny, long long nz, float level,
                                                    const unsigned char* __restrict__ ccounts, const long long* __restrict__ cscan,
                                                    const long long* __restrict__ escan, const long long* __restrict__ totals,
@@ -373,6 +379,16 @@ int mofa_iso_emit(const float* grid, int64_t nx, int64_t ny, int64_t nz, const f
     hipLaunchKernelGGL(k_iso_faces, dim3(blocks_of(l.n_cells)), dim3(256), 0, st, grid, (long long)nx, (long long)ny, (long long)nz, level,
                        ccounts, cscan, escan, totals, faces);
     return check_launch("k_iso_vertices / k_iso_faces");
+}
+
+int mofa_iso_edge_ids(int64_t nx, int64_t ny, int64_t nz, const void* workspace, int64_t* edge_ids, void* stream) {
+    MOFA_REQUIRE(workspace && edge_ids, "iso_edge_ids: null pointer");
+    MOFA_ISO_GRID("iso_edge_ids");
+    const IsoLayout l = iso_layout(nx, ny, nz);
+    const char* ws = (const char*)workspace;
+    hipLaunchKernelGGL(k_iso_edge_ids, dim3(blocks_of(l.n_edges)), dim3(256), 0, (hipStream_t)stream, l.n_edges,
+                       (const unsigned char*)(ws + l.eflags), (const long long*)(ws + l.escan), (const long long*)(ws + l.totals), edge_ids);
+    return check_launch("k_iso_edge_ids");
 }
 
 }  // extern "C"

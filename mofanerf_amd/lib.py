@@ -70,6 +70,14 @@ SIGNATURES = {
     "mofa_band_grow": (C.c_int, [_i64, _i64, _i64, _i32, _fp, C.c_float, _fp, _i64, _fp, _fp]),
     "mofa_band_count": (C.c_int, [_i64, _i64, _i64, _i32, _fp, C.c_float, _fp, _i64, _fp, _fp, _fp, _fp]),
     "mofa_band_emit": (C.c_int, [_i64, _i64, _i64, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float), _fp, C.c_float, _fp, _i64, _fp, _fp, _fp, _fp, _fp]),
+    "mofa_iso_edge_ids": (C.c_int, [_i64, _i64, _i64, _fp, _fp, _fp]),
+    "mofa_edge_points": (C.c_int, [_i64, _i64, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), _fp, _fp, _fp, _i64, _i64, _i32, _fp, _fp, _fp]),
+    "mofa_edge_bracket_init": (C.c_int, [_fp, _fp, C.c_float, _i64, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "mofa_edge_bracket_update": (C.c_int, [_fp, C.c_float, _i64, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "mofa_edge_place": (C.c_int, [_i64, _i64, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), _fp, _fp, _fp, _fp, _fp, C.c_float, _i64, _fp, _fp,
+                                  _fp]),
+    "mofa_fd_points": (C.c_int, [_fp, C.POINTER(C.c_float), _i64, _i64, _fp, _fp]),
+    "mofa_fd_normals": (C.c_int, [_fp, C.POINTER(C.c_float), _i64, _fp, _fp, _fp]),
     "mofa_occ_workspace_bytes": (_sz, [_i64]),
     "mofa_occ_cells": (C.c_int, [_fp, _i64, _i64, _i64, C.c_float, _i32, _fp, _fp]),
     "mofa_occ_dilate": (C.c_int, [_fp, _i64, _i64, _i64, _i32, _fp, _fp, _fp]),

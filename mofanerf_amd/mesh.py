@@ -1,6 +1,7 @@
 """Geometry export: the grid of a density query, the iso-surface of a density grid on the GPU (``mofa_iso_count`` / ``mofa_iso_emit``,
 marching tetrahedra on the Freudenthal split), the same mesh from a narrow band of bricks around the surface (``band_surface``,
-``mofa_band_*``), a binary PLY writer / reader, and the way back from a mesh to a camera: a GPU z-buffer rasteriser (``rasterize``,
+``mofa_band_*``), the refinement of that mesh's vertices onto the level by bisection along their lattice edges and central-difference
+density normals (``refine_vertices``, ``density_normals``, ``mofa_edge_*`` / ``mofa_fd_*``), a binary PLY writer / reader, and the way back from a mesh to a camera: a GPU z-buffer rasteriser (``rasterize``,
 ``mofa_raster_*``) whose depth is comparable with ``Renderer.render_geometry``'s, and ``depth_agreement`` between the two.
 
 ``Renderer.query_density`` and ``Renderer.extract_mesh`` are the user-facing entry points; this module holds the pieces they share.
@@ -46,10 +47,11 @@ def grid_points(resolution, lo, step, first: int, n: int, out: torch.Tensor) -> 
     return out
 
 
-def iso_surface(grid: torch.Tensor, level: float, lo, step) -> Tuple[torch.Tensor, torch.Tensor]:
+def iso_surface(grid: torch.Tensor, level: float, lo, step, edge_ids: bool = False):
     """Triangle mesh of ``{grid >= level}`` for a density grid ``[nx,ny,nz]`` whose sample (i,j,k) sits at lo + (i,j,k) * step:
     ``verts [V,3] float32``, ``faces [F,3] int32`` on the grid's device.  Count, one host read of (V, F), emit.  The grid must be
-    finite (a non-finite sample next to the surface has no position)."""
+    finite (a non-finite sample next to the surface has no position).  ``edge_ids=True`` appends ``edge_ids [V] int64``, the lattice
+    edge ``7 idx + dir`` each vertex sits on (``mofa_iso_edge_ids``; what :func:`refine_vertices` takes)."""
     if grid.dim() != 3:
         raise lib.MofaError(f"iso_surface: want a [nx,ny,nz] grid, got {tuple(grid.shape)}")
     level = float(level)
@@ -75,7 +77,12 @@ def iso_surface(grid: torch.Tensor, level: float, lo, step) -> Tuple[torch.Tenso
     if V and F:
         lib.check(L.mofa_iso_emit(lib.ptr(g), nx, ny, nz, _f3(lo), _f3(step), level, ws.data_ptr(), lib.ptr(verts), faces.data_ptr(),
                                   lib.stream()), "mofa_iso_emit")
-    return verts, faces
+    if not edge_ids:
+        return verts, faces
+    ids = torch.empty(V, dtype=torch.int64, device=g.device)
+    if V:
+        lib.check(L.mofa_iso_edge_ids(nx, ny, nz, ws.data_ptr(), ids.data_ptr(), lib.stream()), "mofa_iso_edge_ids")
+    return verts, faces, ids
 
 
 BRICKS = (4, 8, 16)
@@ -197,6 +204,132 @@ def band_surface(density_fn, resolution, lo, step, level, brick, chunk, verify=N
     if timing:
         stats["times"] = times
     return verts, faces, edge_ids, stats
+
+
+MAX_REFINE = 20      # halvings of an edge: t_m = 0.5 (t_lo + t_hi) stays exact in float32 for 23
+_COUNT_NAMES = ("no_straddle", "non_finite", "refused", "zero_normal")       # MOFA_REFINE_* of include/mofanerf_hip.h
+
+
+def _density_chunks(who, density_fn, pts, out, chunk):
+    """out[i] = density_fn(pts[i]), asked for in calls of at most ``chunk`` points."""
+    for i in range(0, pts.shape[0], chunk):
+        p = pts[i:i + chunk]
+        d = density_fn(p)
+        if not torch.is_tensor(d) or d.shape != (p.shape[0],) or d.dtype != torch.float32 or d.device != pts.device:
+            raise lib.MofaError(f"{who}: density_fn must return [{p.shape[0]}] float32 on {pts.device}, got "
+                                f"{getattr(d, 'shape', type(d))} {getattr(d, 'dtype', '')} {getattr(d, 'device', '')}")
+        out[i:i + p.shape[0]] = d
+
+
+def refine_vertices(density_fn, edge_ids: torch.Tensor, resolution, lo, step, level, iterations, chunk, verify=None):
+    """Move every vertex of :func:`iso_surface` / :func:`band_surface` along its lattice edge onto ``{density = level}`` by bisection
+    (``mofa_edge_*``): ``edge_ids [V] int64`` names the edges, ``density_fn`` is :func:`band_surface`'s (same point, same bits; at most
+    ``chunk`` points per call).  The two ends of every edge are evaluated (they must reproduce the grid's densities: they straddle the
+    level), then ``iterations`` (0 .. 20) times the midpoint of the bracket, which replaces the end on its side of the level; the vertex is
+    the linear interpolation inside the final bracket, so ``iterations = 0`` gives the extraction's own vertices bit for bit and k
+    iterations place a vertex as a grid ``2^k`` times finer along the edge would.  Faces, numbering and topology are untouched.
+    ``verify()``, if given, runs after each round's densities and before a kernel reads them.
+
+    Returns ``(verts [V,3] float32, stats)``; ``stats``: ``evaluations`` ((2 + iterations) V), the final brackets ``t_lo``, ``t_hi``,
+    ``s_lo``, ``s_hi`` ([V] float32 GPU) and ``bracket_width`` (2^-iterations).  Raises ``MofaError`` when an edge's ends do not straddle
+    the level (``density_fn`` did not reproduce the grid's bits), when a density is not finite, or when an edge id is not an edge of the
+    grid."""
+    who = "refine_vertices"
+    nx, ny, nz = (int(v) for v in resolution)
+    level, k, chunk = float(level), int(iterations), int(chunk)
+    if not np.isfinite(level):
+        raise lib.MofaError(f"{who}: the level must be finite (got {level})")
+    if not 0 <= k <= MAX_REFINE or k != iterations:
+        raise lib.MofaError(f"{who}: iterations = {iterations} (want an integer 0 .. {MAX_REFINE})")
+    if chunk < 1:
+        raise lib.MofaError(f"{who}: chunk = {chunk}")
+    if not torch.is_tensor(edge_ids) or not edge_ids.is_cuda or edge_ids.dtype != torch.int64 or edge_ids.dim() != 1 or not edge_ids.is_contiguous():
+        raise lib.MofaError(f"{who}: want contiguous int64 edge_ids [V] on the GPU; there is no CPU path")
+    dev, V = edge_ids.device, int(edge_ids.shape[0])
+    lo3, st3 = _f3(lo), _f3(step)
+    L = lib.load()
+    with torch.cuda.device(dev):
+        stream = lib.stream()
+        t_lo, t_hi, s_lo, s_hi, s_a, s_b = (torch.empty(V, dtype=torch.float32, device=dev) for _ in range(6))
+        verts = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        stats = {"evaluations": (2 + k) * V, "t_lo": t_lo, "t_hi": t_hi, "s_lo": s_lo, "s_hi": s_hi, "bracket_width": 2.0 ** -k}
+        if V == 0:
+            return verts, stats
+        counts = torch.zeros(len(_COUNT_NAMES), dtype=torch.int64, device=dev)
+        buf = torch.zeros(min(chunk, V), 3, dtype=torch.float32, device=dev)      # (zeros: a refused edge's point is never written)
+
+        def evaluate(mode, out):
+            for i in range(0, V, chunk):
+                m = min(chunk, V - i)
+                lib.check(L.mofa_edge_points(nx, ny, nz, lo3, st3, edge_ids.data_ptr(), lib.ptr(t_lo), lib.ptr(t_hi), i, m, mode, lib.ptr(buf),
+                                             counts.data_ptr(), stream), "mofa_edge_points")
+                _density_chunks(who, density_fn, buf[:m], out[i:i + m], chunk)
+            if verify is not None:
+                verify()
+
+        def verdict(what):
+            c = dict(zip(_COUNT_NAMES, (int(v) for v in counts.cpu())))
+            if c["refused"]:
+                raise lib.MofaError(f"{who}: {c['refused']} edge ids are not edges of the {nx} x {ny} x {nz} grid")
+            if c["non_finite"]:
+                raise lib.MofaError(f"{who}: density_fn returned {c['non_finite']} non-finite values at the {what}")
+            if c["no_straddle"]:
+                raise lib.MofaError(f"{who}: the ends of {c['no_straddle']} of {V} edges do not straddle the level {level}: density_fn did "
+                                    f"not reproduce the densities the mesh was extracted from")
+
+        evaluate(0, s_a)
+        evaluate(1, s_b)
+        lib.check(L.mofa_edge_bracket_init(lib.ptr(s_a), lib.ptr(s_b), level, V, lib.ptr(t_lo), lib.ptr(t_hi), lib.ptr(s_lo), lib.ptr(s_hi),
+                                           counts.data_ptr(), stream), "mofa_edge_bracket_init")
+        verdict("edge ends")
+        for _ in range(k):
+            evaluate(2, s_a)
+            lib.check(L.mofa_edge_bracket_update(lib.ptr(s_a), level, V, lib.ptr(t_lo), lib.ptr(t_hi), lib.ptr(s_lo), lib.ptr(s_hi),
+                                                 counts.data_ptr(), stream), "mofa_edge_bracket_update")
+        if k:
+            verdict("bracket midpoints")
+        lib.check(L.mofa_edge_place(nx, ny, nz, lo3, st3, edge_ids.data_ptr(), lib.ptr(t_lo), lib.ptr(t_hi), lib.ptr(s_lo), lib.ptr(s_hi), level,
+                                    V, lib.ptr(verts), counts.data_ptr(), stream), "mofa_edge_place")
+    return verts, stats
+
+
+def density_normals(density_fn, verts: torch.Tensor, step, h_frac: float = 0.5, chunk: int = 1 << 16, verify=None):
+    """Unit normals of the density field at ``verts [V,3]`` from central differences (``mofa_fd_points`` / ``mofa_fd_normals``):
+    ``g_a = (density(v + h_a e_a) - density(v - h_a e_a)) / (2 h_a)`` with ``h = h_frac * step`` per axis (float32), ``n = -g / |g|`` —
+    toward lower density, like the face normals.  ``density_fn`` as for :func:`refine_vertices` (6 V evaluations, at most ``chunk`` points
+    per call); ``verify()`` runs after each group's densities.  Returns ``(normals [V,3] float32, n_zero)``: a vertex whose gradient is
+    zero or not finite gets (0, 0, 0) and is counted."""
+    who = "density_normals"
+    lib.ptr(verts)
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise lib.MofaError(f"{who}: want verts [V,3], got {tuple(verts.shape)}")
+    chunk, h_frac = int(chunk), float(h_frac)
+    if chunk < 1:
+        raise lib.MofaError(f"{who}: chunk = {chunk}")
+    h = (np.float32(h_frac) * np.asarray(step, dtype=np.float32).reshape(3)).astype(np.float32)
+    if not (np.isfinite(h).all() and (h > 0).all()):
+        raise lib.MofaError(f"{who}: h = h_frac * step = {h.tolist()} (want finite and > 0)")
+    h3 = _f3(h)
+    dev, V = verts.device, int(verts.shape[0])
+    normals = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    if V == 0:
+        return normals, 0
+    L = lib.load()
+    with torch.cuda.device(dev):
+        stream = lib.stream()
+        counts = torch.zeros(len(_COUNT_NAMES), dtype=torch.int64, device=dev)
+        group = min(max(chunk // 6, 1), V)                     # vertices per launch: 6 points each
+        pts = torch.empty(6 * group, 3, dtype=torch.float32, device=dev)
+        s = torch.empty(6 * group, dtype=torch.float32, device=dev)
+        for i in range(0, V, group):
+            m = min(group, V - i)
+            lib.check(L.mofa_fd_points(lib.ptr(verts), h3, i, m, lib.ptr(pts), stream), "mofa_fd_points")
+            _density_chunks(who, density_fn, pts[:6 * m], s[:6 * m], chunk)
+            if verify is not None:
+                verify()
+            lib.check(L.mofa_fd_normals(lib.ptr(s), h3, m, lib.ptr(normals[i:i + m]), counts.data_ptr(), stream), "mofa_fd_normals")
+        n_zero = int(counts.cpu()[_COUNT_NAMES.index("zero_normal")])
+    return normals, n_zero
 
 
 def vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
@@ -321,18 +454,26 @@ def _host(t) -> np.ndarray:
     return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
 
 
-def write_ply(path: str, verts, faces, colors=None) -> None:
-    """Binary little-endian PLY: ``float x, y, z`` (+ ``uchar red, green, blue`` from ``colors`` in [0,1] through ``to8b``) per vertex,
-    ``list uchar int vertex_indices`` per face."""
+def write_ply(path: str, verts, faces, colors=None, normals=None) -> None:
+    """Binary little-endian PLY: ``float x, y, z`` (+ ``float nx, ny, nz`` from ``normals``, + ``uchar red, green, blue`` from ``colors``
+    in [0,1] through ``to8b``) per vertex, ``list uchar int vertex_indices`` per face."""
     v = np.ascontiguousarray(_host(verts), dtype=np.float32).reshape(-1, 3)
     f = np.ascontiguousarray(_host(faces), dtype=np.int32).reshape(-1, 3)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     props = "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
     if colors is not None:
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
         props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
     vrec = np.empty(len(v), dtype=fields)
     vrec["x"], vrec["y"], vrec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        nrm = np.ascontiguousarray(_host(normals), dtype=np.float32).reshape(-1, 3)
+        if len(nrm) != len(v):
+            raise ValueError(f"{len(nrm)} normals for {len(v)} vertices")
+        vrec["nx"], vrec["ny"], vrec["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
     if colors is not None:
         c = to8b(_host(colors)).reshape(-1, 3)
         if len(c) != len(v):
@@ -348,8 +489,9 @@ def write_ply(path: str, verts, faces, colors=None) -> None:
         fh.write(frec.tobytes())
 
 
-def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
-    """Read what :func:`write_ply` writes: ``(verts [V,3] float32, faces [F,3] int32, colors [V,3] uint8 or None)``."""
+def read_ply(path: str):
+    """Read what :func:`write_ply` writes: ``(verts [V,3] float32, faces [F,3] int32, colors [V,3] uint8 or None)``, and a fourth
+    element ``normals [V,3] float32`` when the file holds ``nx, ny, nz``."""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
@@ -369,7 +511,7 @@ def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
                 n_f = int(w[2])
         elif w[0] == "property" and element == "vertex":
             vprops.append(w[2])
-    types = {"x": "<f4", "y": "<f4", "z": "<f4", "red": "u1", "green": "u1", "blue": "u1"}
+    types = {"x": "<f4", "y": "<f4", "z": "<f4", "nx": "<f4", "ny": "<f4", "nz": "<f4", "red": "u1", "green": "u1", "blue": "u1"}
     vdt = np.dtype([(p, types[p]) for p in vprops])
     vrec = np.frombuffer(data, dtype=vdt, count=n_v, offset=end)
     frec = np.frombuffer(data, dtype=[("n", "u1"), ("i", "<i4", (3,))], count=n_f, offset=end + n_v * vdt.itemsize)
@@ -377,8 +519,11 @@ def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
         raise ValueError(f"{path}: faces that are not triangles")
     verts = np.stack([vrec["x"], vrec["y"], vrec["z"]], -1).astype(np.float32).reshape(-1, 3)
     colors = np.stack([vrec["red"], vrec["green"], vrec["blue"]], -1).reshape(-1, 3) if "red" in vprops else None
-    return verts, np.ascontiguousarray(frec["i"]).astype(np.int32).reshape(-1, 3), colors
+    faces = np.ascontiguousarray(frec["i"]).astype(np.int32).reshape(-1, 3)
+    if "nx" not in vprops:
+        return verts, faces, colors
+    return verts, faces, colors, np.stack([vrec["nx"], vrec["ny"], vrec["nz"]], -1).astype(np.float32).reshape(-1, 3)
 
 
-__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "vertex_normals", "rasterize", "depth_agreement", "to8b", "write_ply",
+__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "refine_vertices", "density_normals", "vertex_normals", "rasterize", "depth_agreement", "to8b", "write_ply",
                            "read_ply")

@@ -105,7 +105,7 @@ class Renderer(torch.nn.Module):
         self.n_streams = int(os.environ.get("MOFA_STREAMS", "1"))   # concurrent sub-batches of the inference path (render_rays)
         self._streams = {}
         self.png_sink = None      # optional mofanerf_amd.io.PngSink shared by consecutive render_path calls (bulk renders)
-        self.mesh_stats = None    # the statistics of the last narrow-band extract_mesh (mesh.band_surface's, plus "edge_ids")
+        self.mesh_stats = None    # the statistics of the last narrow-band extract_mesh (mesh.band_surface's, plus "edge_ids") or refined one ("refine", "zero_normals")
         self.occupancy_stats = None   # the last render* call with an occupancy grid: {"coarse" / "fine": {"samples", "kept"}}, summed over chunks
 
     @staticmethod
@@ -1094,7 +1094,7 @@ class Renderer(torch.nn.Module):
             return occupancy.occupancy_from_grids(grids, threshold, lo, step, dilate)
 
     def extract_mesh(self, network, *, bounds, resolution, level, shapeCodes, expType=20, expCodes=None, uvCodes=None, colors=False,
-                     netchunk=None, brick=None):
+                     netchunk=None, brick=None, refine=0, normals=None):
         """Triangle mesh of the face: ``{density >= level}`` over the grid of :meth:`query_density`, by marching tetrahedra on the GPU
         (``mofa_iso_count`` / ``mofa_iso_emit``).  Returns ``(verts [V,3] float32, faces [F,3] int32)`` — watertight, normals
         ``(v1 - v0) x (v2 - v0)`` toward lower density — plus, with ``colors=True`` (needs ``uvCodes``), ``colors [V,3]`` in [0,1]:
@@ -1107,26 +1107,52 @@ class Renderer(torch.nn.Module):
         folded codes of :meth:`query_density`.  Every surface component that passes through a brick whose corners straddle the level
         comes out exactly as on the dense grid, its vertices numbered by brick (``self.mesh_stats["edge_ids"]`` gives each vertex's edge
         id; ordering by it gives the dense numbering); smaller components are missed.  ``self.mesh_stats`` keeps the statistics of the
-        last band extraction."""
+        last band extraction.
+
+        ``refine = k`` (1 .. 20, on either path) then moves every vertex along its lattice edge onto the level by k bisection steps on the
+        network's density (``mesh.refine_vertices``: (2 + k) V more density evaluations, the placement of a grid ``2^k`` times finer along
+        each edge; faces and numbering unchanged).  ``normals="density"`` appends ``normals [V,3]`` as the last element of the result: unit
+        normals of the density field by central differences at half a grid step (``mesh.density_normals``, 6 V evaluations; (0, 0, 0)
+        where the gradient vanishes), and the colours then look along them (along the face normals where they are zero);
+        ``normals="faces"`` appends ``mesh.vertex_normals`` instead.  With either, ``self.mesh_stats`` is filled on the dense path too:
+        ``edge_ids``, ``refine`` (``mesh.refine_vertices``' statistics) and ``zero_normals``.  With both at their defaults nothing of
+        this is launched."""
         from . import mesh
         if level is None or not np.isfinite(float(level)):
             raise lib.MofaError(f"extract_mesh: level must be a finite number (got {level})")
         if colors and uvCodes is None:
             raise lib.MofaError("extract_mesh: colors=True needs uvCodes (the texture code the colours are evaluated with)")
+        if normals not in (None, "density", "faces"):
+            raise lib.MofaError(f"extract_mesh: normals = {normals!r} (want None, 'density' or 'faces')")
+        if refine != int(refine) or not 0 <= int(refine) <= mesh.MAX_REFINE:
+            raise lib.MofaError(f"extract_mesh: refine = {refine} (want an integer 0 .. {mesh.MAX_REFINE})")
+        refine = int(refine)
+        extra = refine > 0 or normals is not None
         res, lo, step = mesh.grid_spec(bounds, resolution)
         if brick is None:
             grid = self.query_density(network, bounds=bounds, resolution=resolution, shapeCodes=shapeCodes, expType=expType,
                                       expCodes=expCodes, netchunk=netchunk)
         with torch.no_grad():
-            if brick is None:
+            if brick is None and not extra:
                 verts, faces = mesh.iso_surface(grid, float(level), lo, step)
+            elif brick is None:
+                verts, faces, edge_ids = mesh.iso_surface(grid, float(level), lo, step, edge_ids=True)
+                self.mesh_stats = {"edge_ids": edge_ids}
             else:
                 verts, faces = self._band_mesh(network, res, lo, step, float(level), int(brick), shapeCodes, expType, expCodes, netchunk)
+            nrm = None
+            if extra:
+                verts, nrm = self._refine_mesh(network, verts, faces, res, lo, step, float(level), refine, normals, shapeCodes, expType,
+                                               expCodes, netchunk)
+            tail = () if nrm is None else (nrm,)
             if not colors:
-                return verts, faces
+                return (verts, faces) + tail
             rgb = torch.empty(0, 3, dtype=torch.float32, device=verts.device)
             if verts.shape[0]:
-                vd = (-mesh.vertex_normals(verts, faces)).contiguous()
+                vd = -(nrm if normals == "faces" else mesh.vertex_normals(verts, faces))
+                if normals == "density":                 # look along the density normal; the faces' where the gradient vanishes
+                    vd = torch.where((nrm != 0).any(-1, keepdim=True), -nrm, vd)
+                vd = vd.contiguous()
                 self.decoding_texCodes = uvCodes.to(verts.device)
                 keep, self.netchunk = self.netchunk, int(netchunk if netchunk is not None else self.netchunk)
                 try:
@@ -1135,7 +1161,7 @@ class Renderer(torch.nn.Module):
                     self.netchunk = keep
                 rgb = torch.sigmoid(raw[:, 0, :3])
         self.check_launches(block=True)
-        return verts, faces, rgb
+        return (verts, faces, rgb) + tail
 
     def _band_mesh(self, network, res, lo, step, level, brick, shapeCodes, expType, expCodes, netchunk):
         """extract_mesh's narrow-band path: mesh.band_surface over HipNet.density_points; the statistics go to self.mesh_stats."""
@@ -1152,6 +1178,31 @@ class Renderer(torch.nn.Module):
         stats["edge_ids"] = edge_ids
         self.mesh_stats = stats
         return verts, faces
+
+    def _refine_mesh(self, network, verts, faces, res, lo, step, level, refine, normals, shapeCodes, expType, expCodes, netchunk):
+        """extract_mesh's ``refine`` / ``normals``: mesh.refine_vertices and mesh.density_normals over HipNet.density_points with the
+        folded codes of query_density, on the edges in self.mesh_stats["edge_ids"]; the statistics join self.mesh_stats (``refine``,
+        ``zero_normals``).  Returns (verts, normals or None)."""
+        from . import mesh
+        h, _, chunk, folded = self._density_setup("extract_mesh", network, shapeCodes, expType, expCodes, netchunk)
+
+        def density(pts):
+            out = torch.empty(pts.shape[0], dtype=torch.float32, device=pts.device)
+            h.density_points(pts, out, folded)
+            return out
+
+        def verify():
+            self.check_launches(block=True)
+
+        if refine:
+            verts, self.mesh_stats["refine"] = mesh.refine_vertices(density, self.mesh_stats["edge_ids"], res, lo, step, level, refine, chunk,
+                                                                    verify=verify)
+        nrm = None
+        if normals == "density":
+            nrm, self.mesh_stats["zero_normals"] = mesh.density_normals(density, verts, step, chunk=chunk, verify=verify)
+        elif normals == "faces":
+            nrm = mesh.vertex_normals(verts, faces)
+        return verts, nrm
 
 
 myRenderer = Renderer   # the reference's class name

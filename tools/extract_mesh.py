@@ -15,6 +15,10 @@ meshes are equal after renumbering by edge id:
 
   python tools/extract_mesh.py --synthetic 10 1024 --bounds -1 -1 -1 1 1 1 --resolution 513 513 513 --level 0 --brick 8 \
       --compare-dense --time
+
+``--refine K`` then moves every vertex along its lattice edge onto the level by K bisection steps on the network's density (the
+placement of a grid 2^K times finer along each edge; faces unchanged), and ``--normals density|faces`` writes per-vertex normals
+(``nx ny nz``) to the PLY.
 """
 import argparse
 import itertools
@@ -71,18 +75,29 @@ def main(argv=None):
                     "(with --brick: the band's seed / density / growth / meshing split against the dense path)")
     ap.add_argument("--brick", type=int, default=None, help="narrow-band extraction with bricks of B^3 cells (4, 8 or 16)")
     ap.add_argument("--compare-dense", action="store_true", help="with --brick: also run the dense path and require equal meshes")
+    ap.add_argument("--refine", type=int, default=0, metavar="K", help="move every vertex along its lattice edge onto the level by K "
+                    "bisection steps on the density (0 .. 20; (2 + K) V more density evaluations, faces unchanged)")
+    ap.add_argument("--normals", choices=("density", "faces"), default=None, help="write per-vertex normals to the PLY: the density "
+                    "field's (central differences at half a grid step) or the area-weighted face normals")
     a = ap.parse_args(argv)
     if a.compare_dense and a.brick is None:
         ap.error("--compare-dense needs --brick")
+    if a.compare_dense and a.refine:
+        ap.error("--compare-dense compares the unrefined meshes: drop --refine")
     dev = torch.device("cuda", torch.cuda.current_device())
     render, net, bm, uv, exp = load(a, dev)
     bounds = (tuple(a.bounds[:3]), tuple(a.bounds[3:]))
     res = tuple(a.resolution)
     kw = dict(bounds=bounds, resolution=res, shapeCodes=bm, expType=20, expCodes=exp, netchunk=a.netchunk)
-    out = render.extract_mesh(net, level=a.level, uvCodes=uv if a.colors else None, colors=a.colors, brick=a.brick, **kw)
+    out = render.extract_mesh(net, level=a.level, uvCodes=uv if a.colors else None, colors=a.colors, brick=a.brick, refine=a.refine,
+                              normals=a.normals, **kw)
     verts, faces = out[0], out[1]
-    mesh.write_ply(a.out, verts, faces, out[2] if a.colors else None)
+    mesh.write_ply(a.out, verts, faces, out[2] if a.colors else None, normals=out[-1] if a.normals else None)
     print(f"wrote {a.out}: V = {verts.shape[0]}, F = {faces.shape[0]}")
+    if a.refine:
+        print(f"refined by {a.refine} bisection steps: {render.mesh_stats['refine']['evaluations']} density evaluations at the vertices' edges")
+    if a.normals == "density":
+        print(f"density normals: {render.mesh_stats['zero_normals']} of {verts.shape[0]} vertices have a vanishing gradient")
     if a.brick is not None:
         return band_report(a, render, net, kw, verts, faces)
     if not a.time:

@@ -6,7 +6,9 @@ pixel counts, median and 95th-percentile |depth difference| on the overlap) next
 volume's depth are the same quantity: the ray parameter of the pixel's ``get_rays`` ray.
 
 Writes ``level_<level>_mesh.png`` (head-light shade) and ``level_<level>_mesh_depth.png`` per level and ``volume_depth.png`` into
-``--out``; prints one JSON line at the end.
+``--out``; prints one JSON line at the end.  ``--refine K`` extracts every level a second time with its vertices moved onto the level by
+K bisection steps along their lattice edges (``extract_mesh(refine=K)``) and prints the agreement without and with: the difference is
+what the linear vertex placement contributed to the first number.
 
 Networks come from a checkpoint (``--ckpt``) or seeded synthetic weights (``--synthetic DC WC DF WF``), codes from ``--fit`` or
 ``synth.codes`` — the options of tools/render_geometry.py.  ON SEEDED WEIGHTS THE AGREEMENT NUMBERS MEAN NOTHING ABOUT A TRAINED FACE:
@@ -57,6 +59,8 @@ def main(argv=None):
     lv = ap.add_mutually_exclusive_group(required=True)
     lv.add_argument("--level", type=float, help="one iso-level of the pre-ReLU density (no default: none has been measured)")
     lv.add_argument("--levels", help="several, comma-separated: a,b,c")
+    ap.add_argument("--refine", type=int, default=0, metavar="K", help="also extract every level with its vertices moved onto the level by K "
+                    "bisection steps along their edges (extract_mesh(refine=K)); the agreement is printed without and with")
     ap.add_argument("--size", type=int, default=512, help="frame height = width")
     ap.add_argument("--samples", type=int, nargs=2, default=[64, 128], metavar=("N_SAMPLES", "N_IMPORTANCE"))
     ap.add_argument("--near", type=float, default=8.0)
@@ -100,32 +104,33 @@ def main(argv=None):
     with PngSink() as sink:
         sink.submit(os.path.join(a.out, "volume_depth.png"), (((depth_vol - a.near) / span) * (acc >= a.acc_min))[..., None].expand(H, H, 3))
         for level in levels:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            verts, faces = render.extract_mesh(net, bounds=bounds, resolution=tuple(a.resolution), level=level, shapeCodes=bm, expType=20,
-                                               expCodes=exp, netchunk=a.netchunk, brick=a.brick)[:2]
-            torch.cuda.synchronize()
-            t_extract = (time.perf_counter() - t0) * 1e3
-            t_mesh, all_mesh, (rgb, depth, mask, mex) = median_ms(
-                lambda: render.render_mesh(H, H, K, pose, verts, faces, znear=a.znear), a.warmup, a.frames)
-            t_raster, _, _ = median_ms(lambda: mesh.rasterize(verts, faces, H, H, K, pose, znear=a.znear), a.warmup, a.frames)
-            agree = mesh.depth_agreement(depth, mask, depth_vol, acc, a.acc_min)
-            drawn, culled, degenerate, wave = (int(v) for v in mex["counts"].cpu())
-            row = {"level": level, "V": int(verts.shape[0]), "F": int(faces.shape[0]), "extract_ms": round(t_extract, 2), "render_mesh_ms": t_mesh,
-                   "render_mesh_ms_all": all_mesh, "rasterize_ms": t_raster, "faces_drawn": drawn, "faces_culled": culled,
-                   "faces_degenerate": degenerate, "faces_wave_path": wave, **agree}
-            rows.append(row)
-            print(f"level {level:g}: V = {row['V']}, F = {row['F']} (culled {culled}, degenerate {degenerate}, wavefront path {wave}); extract "
-                  f"{t_extract:.1f} ms, render_mesh {t_mesh:.3f} ms (rasterize alone {t_raster:.3f} ms) against the volume's {t_vol:.1f} ms; "
-                  f"IoU {agree['iou']:.4f} (mesh {agree['n_mesh']}, volume {agree['n_vol']}, both {agree['n_both']}), |depth difference| median "
-                  f"{agree['median_abs']:.5f}, 95 % {agree['p95_abs']:.5f}", flush=True)
-            if culled:
-                print(f"  {culled} faces were culled whole (a vertex nearer than znear or outside the guard band): there is no near-plane clipping")
-            stem = os.path.join(a.out, f"level_{level:g}")
-            sink.submit(stem + "_mesh.png", rgb)
-            sink.submit(stem + "_mesh_depth.png", (((depth - a.near) / span) * mask)[..., None].expand(H, H, 3))
+            for k in ((0, a.refine) if a.refine else (0,)):       # with --refine: the plain mesh, then the refined one
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                verts, faces = render.extract_mesh(net, bounds=bounds, resolution=tuple(a.resolution), level=level, shapeCodes=bm, expType=20,
+                                                   expCodes=exp, netchunk=a.netchunk, brick=a.brick, refine=k)[:2]
+                torch.cuda.synchronize()
+                t_extract = (time.perf_counter() - t0) * 1e3
+                t_mesh, all_mesh, (rgb, depth, mask, mex) = median_ms(
+                    lambda: render.render_mesh(H, H, K, pose, verts, faces, znear=a.znear), a.warmup, a.frames)
+                t_raster, _, _ = median_ms(lambda: mesh.rasterize(verts, faces, H, H, K, pose, znear=a.znear), a.warmup, a.frames)
+                agree = mesh.depth_agreement(depth, mask, depth_vol, acc, a.acc_min)
+                drawn, culled, degenerate, wave = (int(v) for v in mex["counts"].cpu())
+                row = {"level": level, "refine": k, "V": int(verts.shape[0]), "F": int(faces.shape[0]), "extract_ms": round(t_extract, 2), "render_mesh_ms": t_mesh,
+                       "render_mesh_ms_all": all_mesh, "rasterize_ms": t_raster, "faces_drawn": drawn, "faces_culled": culled,
+                       "faces_degenerate": degenerate, "faces_wave_path": wave, **agree}
+                rows.append(row)
+                print(f"level {level:g}{f' refined by {k} bisection steps' if k else ''}: V = {row['V']}, F = {row['F']} (culled {culled}, degenerate {degenerate}, wavefront path {wave}); extract "
+                      f"{t_extract:.1f} ms, render_mesh {t_mesh:.3f} ms (rasterize alone {t_raster:.3f} ms) against the volume's {t_vol:.1f} ms; "
+                      f"IoU {agree['iou']:.4f} (mesh {agree['n_mesh']}, volume {agree['n_vol']}, both {agree['n_both']}), |depth difference| median "
+                      f"{agree['median_abs']:.5f}, 95 % {agree['p95_abs']:.5f}", flush=True)
+                if culled:
+                    print(f"  {culled} faces were culled whole (a vertex nearer than znear or outside the guard band): there is no near-plane clipping")
+                stem = os.path.join(a.out, f"level_{level:g}" + (f"_refine{k}" if k else ""))
+                sink.submit(stem + "_mesh.png", rgb)
+                sink.submit(stem + "_mesh_depth.png", (((depth - a.near) / span) * mask)[..., None].expand(H, H, 3))
     print(json.dumps({"size": H, "samples": a.samples, "angle": a.angle, "radius": a.radius, "near": a.near, "far": a.far, "acc_min": a.acc_min,
-                      "median_threshold": a.median_threshold, "resolution": a.resolution, "brick": a.brick,
+                      "median_threshold": a.median_threshold, "resolution": a.resolution, "brick": a.brick, "refine": a.refine,
                       "wave_min_pixels": mesh.WAVE_MIN_PIXELS, "synthetic_weights": bool(a.synthetic),
                       "agreement_says_nothing_about_a_trained_face": bool(a.synthetic), "render_geometry_ms": t_vol,
                       "render_geometry_ms_all": all_vol, "levels": rows, "out": a.out}))
