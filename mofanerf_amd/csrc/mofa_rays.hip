@@ -27,8 +27,9 @@ __global__ __launch_bounds__(256) void k_get_rays(int H, int W, float fx, float 
     const int j = (int)(pix / W), i = (int)(pix - (long long)j * W);
     float ro[3], rd[3];
     pinhole_ray(i, j, fx, fy, cx, cy, c2w, ro, rd);
-    const float nrm = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(rd[0], rd[0]), __fmul_rn(rd[1], rd[1])),
-                                           __fmul_rn(rd[2], rd[2])));
+    // sqrtf, not __fsqrt_rn: the latter is the hardware's approximate square root here (view directions up to 2 ulp off), sqrtf the correctly
+    // rounded one a host restates (k_point_normals)
+    const float nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(rd[0], rd[0]), __fmul_rn(rd[1], rd[1])), __fmul_rn(rd[2], rd[2])));
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         rays_o[t * 3 + a] = ro[a];

@@ -567,27 +567,30 @@ class Renderer(torch.nn.Module):
 
         def gen(pose):
             n = int(H) * int(W)
-            o, d, v = (torch.empty(n, 3, dtype=torch.float32, device=dev) for _ in range(3))
+            o, d = (torch.empty(n, 3, dtype=torch.float32, device=dev) for _ in range(2))
             if torch.is_tensor(pose):        # stays on the device when it is there already: no device->host->device hop, no host sync
                 pose_t = pose.detach()[:3, :4].to(device=dev, dtype=torch.float32).contiguous()
             else:
                 pose_t = torch.as_tensor(np.asarray(pose), dtype=torch.float32)[:3, :4].contiguous().to(dev)
             lib.check(L.mofa_get_rays(int(H), int(W), _scalar(K[0][0]), _scalar(K[1][1]), _scalar(K[0][2]),
-                                      _scalar(K[1][2]), lib.ptr(pose_t), 0, n, lib.ptr(o), lib.ptr(d), lib.ptr(v),
+                                      _scalar(K[1][2]), lib.ptr(pose_t), 0, n, lib.ptr(o), lib.ptr(d), None,
                                       lib.stream()), "mofa_get_rays")
-            return o, d, v
+            return o, d
 
         if c2w is not None:
-            rays_o, rays_d, viewdirs = gen(c2w)
+            rays_o, rays_d = gen(c2w)
             sh = (int(H), int(W), 3)
         else:
             rays_o, rays_d = rays[0], rays[1]
             sh = tuple(rays_d.shape)
             rays_o = rays_o.reshape(-1, 3).float().to(dev)       # may carry gradients to the camera pose (run_fit.py:281)
             rays_d = rays_d.reshape(-1, 3).float().to(dev)
-            viewdirs = rays_d / torch.norm(rays_d, dim=-1, keepdim=True)
+        # ONE statement of the view directions, the reference's (render_class.py:399-401), for a pose and for given rays alike: a frame
+        # rendered from a pose is, bit for bit, the frame rendered from that pose's rays (mofa_get_rays' own viewdirs output is the
+        # correctly rounded rd / sqrt((x^2 + y^2) + z^2), up to 2 ulp from what torch.norm gives on the device)
+        viewdirs = rays_d / torch.norm(rays_d, dim=-1, keepdim=True)
         if c2w_staticcam is not None:      # visualise the effect of viewdirs only (render_class.py:161-163)
-            rays_o, rays_d, _ = gen(c2w_staticcam)
+            rays_o, rays_d = gen(c2w_staticcam)
         if ndc:                            # forward-facing scenes (render_class.py:166-169); viewdirs stay the world-space ones
             from .rays import ndc_rays
             rays_o, rays_d = ndc_rays(int(H), int(W), _scalar(K[0][0]), 1., rays_o, rays_d)

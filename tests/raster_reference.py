@@ -11,6 +11,7 @@
 import numpy as np
 
 from mofanerf_amd.rays import pose_spherical
+from rays_reference import pose_spherical as generic_pose
 
 f32 = np.float32
 INT32_MAX = 2 ** 31 - 1
@@ -278,6 +279,15 @@ def scene_a():
 def scene_b(pose=(-40.0, 15.0, 3.5)):
     v, f = uv_sphere(24, 32)
     return dict(verts=v, faces=f, H=29, W=37, K=camera(29, 37), c2w=pose34(pose_spherical(*pose)))
+
+
+def scene_c():
+    """Scene B's sphere under an ANISOTROPIC camera — fx = 1.3 W, fy = 0.8 W, off-centre — with a generic pose (azimuth, elevation, roll and
+    a shift off the axis: no rotation entry is 0 or +-1): exchanged focal lengths or principal-point coordinates move every vertex."""
+    v, f = uv_sphere(24, 32)
+    H, W = 29, 37
+    K = np.array([[1.3 * W, 0, W / 2 - 3.25], [0, 0.8 * W, H / 2 + 1.5], [0, 0, 1]], np.float32)
+    return dict(verts=v, faces=f, H=H, W=W, K=K, c2w=generic_pose(-40.0, 15.0, 3.5, 20.0, (0.15, -0.1, 0.2)))
 
 
 def exact_camera(H, W, cx, cy):

@@ -92,14 +92,14 @@ def check_scene(s, attrs=None, znear=1e-3, wmps=(0, MAX)):
     return got
 
 
-# ---- 1. scenes A and B -----------------------------------------------------------------------------------------------------------------
+# ---- 1. scenes A, B and C (C: fx != fy, a generic pose) -----------------------------------------------------------------------------------------------------------------
 _cache = {}
 
 
 def scene_reference(name):
     """(scene, attrs [V,16], {wave_min_pixels: restated frame}) — computed once."""
     if name not in _cache:
-        s = ref.scene_a() if name == "A" else ref.scene_b()
+        s = {"A": ref.scene_a, "B": ref.scene_b, "C": ref.scene_c}[name]()
         attrs = np.random.default_rng(7).normal(size=(len(s["verts"]), 16)).astype(np.float32)
         full = want_frame(s, attrs, wmp=MAX)
         frames = {MAX: full}
@@ -111,7 +111,7 @@ def scene_reference(name):
 
 
 @pytest.mark.parametrize("wmp", sorted({0, 16, DEFAULT, MAX}))
-@pytest.mark.parametrize("name", ["A", "B"])
+@pytest.mark.parametrize("name", ["A", "B", "C"])
 def test_scenes_are_the_restatement_bit_for_bit_on_either_path(name, wmp):
     s, attrs, frames = scene_reference(name)
     want = frames[wmp]

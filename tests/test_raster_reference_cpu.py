@@ -27,7 +27,7 @@ def frames(scene, fault=None, **kw):
     return rast, cast, ref.agreement(rast, cast, s["verts"], s["faces"], s["K"], s["c2w"])
 
 
-SCENES = {"A": ref.scene_a, "B": ref.scene_b, "B_first_pose": lambda: ref.scene_b((25.0, -20.0, 4.0)), "quad": ref.quad_scene,
+SCENES = {"A": ref.scene_a, "B": ref.scene_b, "C": ref.scene_c, "B_first_pose": lambda: ref.scene_b((25.0, -20.0, 4.0)), "quad": ref.quad_scene,
           "quad_doubled": lambda: ref.quad_scene(doubled=True), "behind": ref.behind_scene}
 
 
