@@ -312,6 +312,38 @@ int mofa_edge_place(int64_t nx, int64_t ny, int64_t nz, const float lo[3], const
 int mofa_fd_points(const float* verts, const float h[3], int64_t first, int64_t n, float* pts, void* stream);
 int mofa_fd_normals(const float* s, const float h[3], int64_t n, float* normals, int64_t* counts, void* stream);
 
+/* Connected components of a triangle mesh (verts [V,3] float, faces [F,3] int32; 1 <= V, F <= 2^31 - 1): two faces belong to one
+ * component when they share a vertex INDEX; a degenerate face (a, a, b) still joins a and b.  The caller (mesh.py) drives the passes.
+ * Every kernel checks the indices it dereferences (a face with an index outside [0, V) is skipped), so a bad index is never a GPU fault;
+ * mofa_cc_validate is how the caller learns of one before anything else runs.  No kernel waits on another thread: the only loop whose
+ * trip count depends on the data is the root walk x = parent[x], which strictly decreases.  Integer atomicMin on parent[] is the only
+ * atomic besides the validation's error counter, so the same mesh gives the same bits every time.
+ *   mofa_cc_validate    counts[0] (int64, DEVICE, zeroed by the caller) += the face indices outside [0, V)
+ *   mofa_cc_init        parent[v] = v (int32 [V])
+ *   mofa_cc_hook        for the edges (a, b) and (b, c) of every face: ra = root(a), rb = root(b); if they differ,
+ *                       atomicMin(&parent[max(ra, rb)], min(ra, rb)) and *changed = 1 (int64, DEVICE, zeroed by the caller)
+ *   mofa_cc_compress    parent[v] = root(v).  hook + compress are repeated until a pass leaves *changed at 0: then parent[v] is the
+ *                       smallest vertex index of v's component
+ *   mofa_cc_face_terms  terms [F,2] (double), each operation rounded separately in fp64 from the fp32 coordinates:
+ *                       terms[f][0] = 0.5 |(v1 - v0) x (v2 - v0)|, terms[f][1] = v0 . (v1 x v2) / 6
+ *   mofa_cc_seg_sum     out [n_segments,2] (double): out[s] = the sum of the rows seg_start[s] .. seg_end[s] - 1 (int64, DEVICE, clipped to
+ *                       [0, N)) of in [N,2], read through perm [N] (int64, DEVICE; NULL = the identity) — one workgroup per segment, a fixed
+ *                       order and a fixed tree, the same bits every time.  longest >= every segment's length (rows beyond it are not summed).
+ *   mofa_cc_seg_minmax  out [n_segments,2,3] (float) = the exact [min xyz, max xyz] over each segment's rows of in — points [N,3] (boxes = 0)
+ *                       or boxes [N,2,3] (boxes != 0) —, walked like mofa_cc_seg_sum; floats are compared by their order-preserving integer
+ *                       key (-0 < +0).  An empty segment gets NaN.
+ *   mofa_cc_remap       out[i] = vmap[in[i]] for n int32 indices (vmap int32 [V]); -1 for an index outside [0, V) */
+int mofa_cc_validate(const int32_t* faces, int64_t F, int64_t V, int64_t* counts, void* stream);
+int mofa_cc_init(int32_t* parent, int64_t V, void* stream);
+int mofa_cc_hook(const int32_t* faces, int64_t F, int64_t V, int32_t* parent, int64_t* changed, void* stream);
+int mofa_cc_compress(int32_t* parent, int64_t V, void* stream);
+int mofa_cc_face_terms(const float* verts, const int32_t* faces, int64_t F, int64_t V, double* terms, void* stream);
+int mofa_cc_seg_sum(const double* in, const int64_t* perm, int64_t N, const int64_t* seg_start, const int64_t* seg_end, int64_t n_segments,
+                    int64_t longest, double* out, void* stream);
+int mofa_cc_seg_minmax(const float* in, int32_t boxes, const int64_t* perm, int64_t N, const int64_t* seg_start, const int64_t* seg_end,
+                       int64_t n_segments, int64_t longest, float* out, void* stream);
+int mofa_cc_remap(const int32_t* in, int64_t n, const int32_t* vmap, int64_t V, int32_t* out, void* stream);
+
 /* ---- occupancy-culled rendering: skip the network where an occupancy grid says the space is empty ---------------------------------
  * The grid lives on the lattice of mofa_grid_points (nx x ny x nz samples at lo + (i,j,k) step): (nx-1)(ny-1)(nz-1) cells, one byte
  * each (0 / 1), cell index (i (ny-1) + j) (nz-1) + k.  The lattice needs 2 <= n < 2^24 per axis and fewer than 2^31 cells.

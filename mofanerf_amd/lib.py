@@ -78,6 +78,14 @@ SIGNATURES = {
                                   _fp]),
     "mofa_fd_points": (C.c_int, [_fp, C.POINTER(C.c_float), _i64, _i64, _fp, _fp]),
     "mofa_fd_normals": (C.c_int, [_fp, C.POINTER(C.c_float), _i64, _fp, _fp, _fp]),
+    "mofa_cc_validate": (C.c_int, [_fp, _i64, _i64, _fp, _fp]),
+    "mofa_cc_init": (C.c_int, [_fp, _i64, _fp]),
+    "mofa_cc_hook": (C.c_int, [_fp, _i64, _i64, _fp, _fp, _fp]),
+    "mofa_cc_compress": (C.c_int, [_fp, _i64, _fp]),
+    "mofa_cc_face_terms": (C.c_int, [_fp, _fp, _i64, _i64, _fp, _fp]),
+    "mofa_cc_seg_sum": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _i64, _i64, _fp, _fp]),
+    "mofa_cc_seg_minmax": (C.c_int, [_fp, _i32, _fp, _i64, _fp, _fp, _i64, _i64, _fp, _fp]),
+    "mofa_cc_remap": (C.c_int, [_fp, _i64, _fp, _i64, _fp, _fp]),
     "mofa_occ_workspace_bytes": (_sz, [_i64]),
     "mofa_occ_cells": (C.c_int, [_fp, _i64, _i64, _i64, C.c_float, _i32, _fp, _fp]),
     "mofa_occ_dilate": (C.c_int, [_fp, _i64, _i64, _i64, _i32, _fp, _fp, _fp]),

@@ -3,6 +3,8 @@ marching tetrahedra on the Freudenthal split), the same mesh from a narrow band 
 ``mofa_band_*``), the refinement of that mesh's vertices onto the level by bisection along their lattice edges and central-difference
 density normals (``refine_vertices``, ``density_normals``, ``mofa_edge_*`` / ``mofa_fd_*``), a binary PLY writer / reader, and the way back from a mesh to a camera: a GPU z-buffer rasteriser (``rasterize``,
 ``mofa_raster_*``) whose depth is comparable with ``Renderer.render_geometry``'s, and ``depth_agreement`` between the two.
+``components`` labels a mesh's connected components (``mofa_cc_*``) with their sizes, areas, signed volumes and boxes;
+``select_components`` / ``keep_components`` drop the floaters among them.
 
 ``Renderer.query_density`` and ``Renderer.extract_mesh`` are the user-facing entry points; this module holds the pieces they share.
 The mesh is watertight and consistently oriented (normals toward lower density); vertices and faces come out in a fixed order with
@@ -345,6 +347,204 @@ def vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
 
 
 INT32_MAX = 2 ** 31 - 1
+# hook + compress passes of components() before it gives up: a guard against a faulty kernel, not a tuning knob (a 100,003-vertex strip
+# with random numbering needs 12, lattice-ordered iso-surfaces 3-4: about 0.7 log2 V)
+MAX_CC_PASSES = 64
+CC_CHUNK = 1024      # elements per first-level reduction of a component's box (vertices) and area / volume (faces)
+
+
+def _mesh_tensors(who, verts, faces):
+    """(V, F, device) of a mesh on the GPU: contiguous float32 verts [V,3], contiguous int32 faces [F,3], V, F < 2^31."""
+    lib.ptr(verts)
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise lib.MofaError(f"{who}: want verts [V,3], got {tuple(verts.shape)}")
+    if not torch.is_tensor(faces) or not faces.is_cuda:
+        raise lib.MofaError(f"{who}: the HIP path needs tensors on the GPU (got CPU faces); there is no CPU fallback")
+    if faces.dtype != torch.int32 or not faces.is_contiguous() or faces.dim() != 2 or faces.shape[1] != 3:
+        raise lib.MofaError(f"{who}: want contiguous int32 faces [F,3], got {faces.dtype} {tuple(faces.shape)} contiguous={faces.is_contiguous()}")
+    if faces.device != verts.device:
+        raise lib.MofaError(f"{who}: verts on {verts.device}, faces on {faces.device}")
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if V > INT32_MAX or F > INT32_MAX:
+        raise lib.MofaError(f"{who}: {V} vertices / {F} faces exceed the int32 indices (2^31 - 1)")
+    return V, F, verts.device
+
+
+def _cc_runs(counts, offset):
+    """For elements sorted by label, ``counts [C]`` per label, the first label's run starting at ``offset``: (run [C+1], the run ends;
+    first_chunk [C+1], the index of each label's first chunk of CC_CHUNK elements; chunks per label [C])."""
+    n = counts.shape[0]
+    run = torch.full((n + 1,), int(offset), dtype=torch.int64, device=counts.device)
+    run[1:] += torch.cumsum(counts, 0)
+    per_label = (counts + (CC_CHUNK - 1)) // CC_CHUNK
+    first_chunk = torch.zeros(n + 1, dtype=torch.int64, device=counts.device)
+    first_chunk[1:] = torch.cumsum(per_label, 0)
+    return run, first_chunk, per_label
+
+
+def _cc_chunks(run, first_chunk, per_label, n_chunks):
+    """(start [n_chunks], end [n_chunks]) of every chunk: label l's j-th chunk is run[l] + CC_CHUNK j .. , cut at run[l + 1]."""
+    i64 = dict(dtype=torch.int64, device=run.device)
+    label_of = torch.repeat_interleave(torch.arange(per_label.shape[0], **i64), per_label, output_size=n_chunks)
+    start = run[label_of] + CC_CHUNK * (torch.arange(n_chunks, **i64) - first_chunk[label_of])
+    return start, torch.minimum(start + CC_CHUNK, run[label_of + 1])
+
+
+def components(verts: torch.Tensor, faces: torch.Tensor, timing: bool = False) -> dict:
+    """Connected components of a triangle mesh on the GPU (``mofa_cc_*``): two faces belong to one component when they share a vertex
+    index (a degenerate face ``(a, a, b)`` still joins a and b).  Components are numbered 0 .. C-1 in the order of their smallest vertex
+    index; a vertex no face references gets label -1 and belongs to none.  Returns a dict: ``n_components`` (int), ``vertex_labels [V]
+    int32``, ``face_labels [F] int32`` (the label of the face's first vertex), ``n_verts`` / ``n_faces`` ``[C] int64``, ``area [C]
+    float64`` (sum of 0.5 |(v1 - v0) x (v2 - v0)|), ``volume [C] float64`` (sum of v0 . (v1 x v2) / 6, signed: with the orientation of
+    :func:`iso_surface` a solid blob is positive, a cavity negative), ``bbox [C,2,3] float32`` (exact min and max), ``unreferenced`` (int)
+    and ``passes`` (hook + compress passes run, the last of which changed nothing).  Tensors are on the mesh's device.
+
+    The face indices are validated first (one host read): an index outside [0, V) raises ``MofaError`` with the count and nothing else
+    is launched.  Labels come from integer ``atomicMin`` only, the boxes and the sums from fixed-order two-level reductions over the vertices
+    and the faces sorted by label, so the same mesh gives the same bytes every time.  ``V == 0`` or ``F == 0`` gives zero components without a launch.
+    ``timing=True`` adds ``times``: seconds of the ``validate``, ``labels`` (the passes), ``number`` (dense labels and counts), ``bbox``
+    (sort, the two-level min / max) and ``sums`` (terms, sort, the two-level sums) phases, each ended by a device synchronisation."""
+    who = "components"
+    V, F, dev = _mesh_tensors(who, verts, faces)
+    if V == 0 or F == 0:
+        return {"n_components": 0, "vertex_labels": torch.full((V,), -1, dtype=torch.int32, device=dev),
+                "face_labels": torch.full((F,), -1, dtype=torch.int32, device=dev), "n_verts": torch.zeros(0, dtype=torch.int64, device=dev),
+                "n_faces": torch.zeros(0, dtype=torch.int64, device=dev), "area": torch.zeros(0, dtype=torch.float64, device=dev),
+                "volume": torch.zeros(0, dtype=torch.float64, device=dev), "bbox": torch.zeros(0, 2, 3, dtype=torch.float32, device=dev),
+                "unreferenced": V, "passes": 0}
+    L = lib.load()
+    i64 = dict(dtype=torch.int64, device=dev)
+    times, clock = {}, [time.perf_counter()]
+
+    def lap(phase):
+        if timing:
+            torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            times[phase] = now - clock[0]
+            clock[0] = now
+
+    with torch.cuda.device(dev):
+        stream = lib.stream()
+        lap("start")
+        counts = torch.zeros(1, **i64)
+        lib.check(L.mofa_cc_validate(faces.data_ptr(), F, V, counts.data_ptr(), stream), "mofa_cc_validate")
+        bad = int(counts.cpu()[0])
+        if bad:
+            raise lib.MofaError(f"{who}: {bad} of the {3 * F} face indices lie outside [0, {V})")
+        lap("validate")
+        # labels: parent[v] = the smallest vertex index of v's component
+        parent = torch.empty(V, dtype=torch.int32, device=dev)
+        changed = torch.zeros(MAX_CC_PASSES, **i64)                  # one word per pass: nothing to zero in between
+        lib.check(L.mofa_cc_init(parent.data_ptr(), V, stream), "mofa_cc_init")
+        passes = 0
+        while True:
+            if passes == MAX_CC_PASSES:
+                raise lib.MofaError(f"{who}: the labels of {V} vertices / {F} faces did not settle in {MAX_CC_PASSES} passes")
+            lib.check(L.mofa_cc_hook(faces.data_ptr(), F, V, parent.data_ptr(), changed.data_ptr() + 8 * passes, stream), "mofa_cc_hook")
+            lib.check(L.mofa_cc_compress(parent.data_ptr(), V, stream), "mofa_cc_compress")
+            passes += 1
+            if not int(changed[passes - 1].cpu()):                   # (one 8-byte read per pass)
+                break
+        lap("labels")
+        # dense labels: rank of the root among the referenced roots
+        referenced = torch.zeros(V, dtype=torch.bool, device=dev)
+        referenced[faces.reshape(-1).long()] = True
+        is_root = (parent == torch.arange(V, dtype=torch.int32, device=dev)) & referenced
+        rank = torch.cumsum(is_root, 0, dtype=torch.int64) - 1
+        n_c, n_ref = (int(v) for v in torch.stack([rank[-1] + 1, referenced.sum()]).cpu())
+        vertex_labels = torch.where(referenced, rank[parent.long()], -1).to(torch.int32)
+        face_labels = vertex_labels[faces[:, 0].long()].contiguous()
+        n_verts = torch.bincount(vertex_labels[referenced].long(), minlength=n_c)
+        n_faces = torch.bincount(face_labels.long(), minlength=n_c)
+        lap("number")
+        # statistics: the elements stably sorted by label, every label's run reduced in chunks of CC_CHUNK elements from its start, then
+        # every label's chunks — one workgroup per chunk / per label, a fixed order inside each, no atomics
+        f_run, f_first, f_count = _cc_runs(n_faces, 0)
+        v_run, v_first, v_count = _cc_runs(n_verts, V - n_ref)                      # (sorted by label, the unreferenced -1 come first)
+        nf_chunks, f_most, nv_chunks, v_most = (int(v) for v in torch.stack([f_first[-1], f_count.max(), v_first[-1], v_count.max()]).cpu())
+        order = torch.sort(vertex_labels, stable=True).indices
+        start, end = _cc_chunks(v_run, v_first, v_count, nv_chunks)
+        boxes = torch.empty(nv_chunks, 2, 3, dtype=torch.float32, device=dev)
+        lib.check(L.mofa_cc_seg_minmax(lib.ptr(verts), 0, order.data_ptr(), V, start.data_ptr(), end.data_ptr(), nv_chunks, CC_CHUNK,
+                                       lib.ptr(boxes), stream), "mofa_cc_seg_minmax")
+        bbox = torch.empty(n_c, 2, 3, dtype=torch.float32, device=dev)
+        start, end = v_first[:-1].contiguous(), v_first[1:].contiguous()
+        lib.check(L.mofa_cc_seg_minmax(lib.ptr(boxes), 1, None, nv_chunks, start.data_ptr(), end.data_ptr(), n_c, v_most, lib.ptr(bbox), stream),
+                  "mofa_cc_seg_minmax")
+        lap("bbox")
+        terms = torch.empty(F, 2, dtype=torch.float64, device=dev)
+        lib.check(L.mofa_cc_face_terms(lib.ptr(verts), faces.data_ptr(), F, V, terms.data_ptr(), stream), "mofa_cc_face_terms")
+        order = torch.sort(face_labels, stable=True).indices
+        start, end = _cc_chunks(f_run, f_first, f_count, nf_chunks)
+        partial = torch.empty(nf_chunks, 2, dtype=torch.float64, device=dev)
+        lib.check(L.mofa_cc_seg_sum(terms.data_ptr(), order.data_ptr(), F, start.data_ptr(), end.data_ptr(), nf_chunks, CC_CHUNK,
+                                    partial.data_ptr(), stream), "mofa_cc_seg_sum")
+        sums = torch.empty(n_c, 2, dtype=torch.float64, device=dev)
+        start, end = f_first[:-1].contiguous(), f_first[1:].contiguous()
+        lib.check(L.mofa_cc_seg_sum(partial.data_ptr(), None, nf_chunks, start.data_ptr(), end.data_ptr(), n_c, f_most, sums.data_ptr(), stream),
+                  "mofa_cc_seg_sum")
+        lap("sums")
+    out = {"n_components": n_c, "vertex_labels": vertex_labels, "face_labels": face_labels, "n_verts": n_verts, "n_faces": n_faces,
+           "area": sums[:, 0].contiguous(), "volume": sums[:, 1].contiguous(), "bbox": bbox, "unreferenced": V - n_ref, "passes": passes}
+    if timing:
+        times.pop("start")
+        out["times"] = times
+    return out
+
+
+def select_components(stats: dict, keep) -> torch.Tensor:
+    """A keep mask ``[C] bool`` over the components of :func:`components`: ``"largest"`` (most faces; a tie keeps the lowest label), an
+    integer ``n`` (every component with ``n_faces >= n``), a callable ``keep(stats)`` that returns a mask, or the mask itself."""
+    n_c, n_faces = int(stats["n_components"]), stats["n_faces"]
+    dev = n_faces.device
+    if isinstance(keep, str):
+        if keep != "largest":
+            raise lib.MofaError(f"select_components: keep = {keep!r} (want 'largest', a face count, a callable or a mask)")
+        mask = torch.zeros(n_c, dtype=torch.bool, device=dev)
+        if n_c:
+            mask[torch.nonzero(n_faces == n_faces.max())[0, 0]] = True
+        return mask
+    if isinstance(keep, (int, np.integer)) and not isinstance(keep, (bool, np.bool_)):
+        if keep < 0:
+            raise lib.MofaError(f"select_components: keep = {keep} (a face count cannot be negative)")
+        return n_faces >= int(keep)
+    if callable(keep):
+        keep = keep(stats)
+    mask = torch.as_tensor(keep)
+    if mask.dtype != torch.bool or mask.shape != (n_c,):
+        raise lib.MofaError(f"select_components: want a bool mask [{n_c}], got {mask.dtype} {tuple(mask.shape)}")
+    return mask.to(dev)
+
+
+def keep_components(verts: torch.Tensor, faces: torch.Tensor, stats: dict, mask: torch.Tensor, *per_vertex: torch.Tensor):
+    """Compact a mesh to the components ``mask [C] bool`` keeps (``stats`` of :func:`components` on the same mesh): the kept vertices in
+    their old order (unreferenced vertices are dropped), the kept faces in their old order with their indices remapped
+    (``mofa_cc_remap``), and any ``per_vertex`` tensors ``[V, ...]`` (edge ids, colours, normals) carried through the same map.
+    Returns ``(verts, faces, *per_vertex)``; kept vertices keep their bits."""
+    who = "keep_components"
+    V, F, dev = _mesh_tensors(who, verts, faces)
+    n_c, vl, fl = int(stats["n_components"]), stats["vertex_labels"], stats["face_labels"]
+    if vl.shape != (V,) or fl.shape != (F,) or vl.device != dev:
+        raise lib.MofaError(f"{who}: the statistics describe {tuple(vl.shape)} vertices / {tuple(fl.shape)} faces on {vl.device}, the mesh has "
+                            f"{V} / {F} on {dev}")
+    if not torch.is_tensor(mask) or mask.dtype != torch.bool or mask.shape != (n_c,) or mask.device != dev:
+        raise lib.MofaError(f"{who}: want a bool mask [{n_c}] on {dev} (select_components gives one)")
+    for p in per_vertex:
+        if not torch.is_tensor(p) or p.dim() < 1 or p.shape[0] != V or p.device != dev:
+            raise lib.MofaError(f"{who}: want per-vertex tensors [{V}, ...] on {dev}, got {tuple(getattr(p, 'shape', ()))}")
+    if n_c == 0:
+        return (verts[:0], faces[:0]) + tuple(p[:0] for p in per_vertex)
+    with torch.cuda.device(dev):
+        vkeep = (vl >= 0) & mask[vl.clamp(min=0).long()]
+        fkeep = mask[fl.long()]
+        vmap = torch.where(vkeep, torch.cumsum(vkeep, 0, dtype=torch.int32) - 1, -1).to(torch.int32)
+        old = faces[fkeep].contiguous()
+        new = torch.empty_like(old)
+        if old.numel():
+            lib.check(lib.load().mofa_cc_remap(old.data_ptr(), old.numel(), vmap.data_ptr(), V, new.data_ptr(), lib.stream()), "mofa_cc_remap")
+        return (verts[vkeep], new) + tuple(p[vkeep] for p in per_vertex)
+
+
 # faces whose clipped box of samples holds at least this many pixels are walked one wavefront per face (mofa_raster_faces); the choice
 # changes no bit of the frame.  profiles/mesh_raster.md holds the sweep it comes from.
 WAVE_MIN_PIXELS = 64
@@ -525,5 +725,5 @@ def read_ply(path: str):
     return verts, faces, colors, np.stack([vrec["nx"], vrec["ny"], vrec["nz"]], -1).astype(np.float32).reshape(-1, 3)
 
 
-__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "refine_vertices", "density_normals", "vertex_normals", "rasterize", "depth_agreement", "to8b", "write_ply",
+__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "refine_vertices", "density_normals", "vertex_normals", "components", "select_components", "keep_components", "rasterize", "depth_agreement", "to8b", "write_ply",
                            "read_ply")

@@ -105,7 +105,7 @@ class Renderer(torch.nn.Module):
         self.n_streams = int(os.environ.get("MOFA_STREAMS", "1"))   # concurrent sub-batches of the inference path (render_rays)
         self._streams = {}
         self.png_sink = None      # optional mofanerf_amd.io.PngSink shared by consecutive render_path calls (bulk renders)
-        self.mesh_stats = None    # the statistics of the last narrow-band extract_mesh (mesh.band_surface's, plus "edge_ids") or refined one ("refine", "zero_normals")
+        self.mesh_stats = None    # the statistics of the last narrow-band extract_mesh (mesh.band_surface's, plus "edge_ids") or refined one ("refine", "zero_normals") or filtered one ("components")
         self.occupancy_stats = None   # the last render* call with an occupancy grid: {"coarse" / "fine": {"samples", "kept"}}, summed over chunks
 
     @staticmethod
@@ -1097,7 +1097,7 @@ class Renderer(torch.nn.Module):
             return occupancy.occupancy_from_grids(grids, threshold, lo, step, dilate)
 
     def extract_mesh(self, network, *, bounds, resolution, level, shapeCodes, expType=20, expCodes=None, uvCodes=None, colors=False,
-                     netchunk=None, brick=None, refine=0, normals=None):
+                     netchunk=None, brick=None, refine=0, normals=None, components=None):
         """Triangle mesh of the face: ``{density >= level}`` over the grid of :meth:`query_density`, by marching tetrahedra on the GPU
         (``mofa_iso_count`` / ``mofa_iso_emit``).  Returns ``(verts [V,3] float32, faces [F,3] int32)`` — watertight, normals
         ``(v1 - v0) x (v2 - v0)`` toward lower density — plus, with ``colors=True`` (needs ``uvCodes``), ``colors [V,3]`` in [0,1]:
@@ -1119,8 +1119,17 @@ class Renderer(torch.nn.Module):
         where the gradient vanishes), and the colours then look along them (along the face normals where they are zero);
         ``normals="faces"`` appends ``mesh.vertex_normals`` instead.  With either, ``self.mesh_stats`` is filled on the dense path too:
         ``edge_ids``, ``refine`` (``mesh.refine_vertices``' statistics) and ``zero_normals``.  With both at their defaults nothing of
-        this is launched."""
+        this is launched.
+
+        ``components="largest"`` or ``components=n`` removes floaters right after the extraction, before refinement, normals and colours
+        (which then run on the kept vertices only): the mesh's connected components are labelled (``mesh.components``) and only the one
+        with the most faces, or every one with at least ``n`` faces, is kept (``mesh.keep_components``; kept vertices and faces stay in
+        their order).  ``self.mesh_stats["components"]`` then holds the statistics of the unfiltered mesh plus ``kept`` (the mask), and
+        ``self.mesh_stats["edge_ids"]`` is filtered with the vertices.  ``None`` launches nothing and returns the same bytes as before."""
         from . import mesh
+        if components is not None and components != "largest" and not (isinstance(components, (int, np.integer)) and
+                                                                       not isinstance(components, (bool, np.bool_)) and components >= 1):
+            raise lib.MofaError(f"extract_mesh: components = {components!r} (want None, 'largest' or a face count >= 1)")
         if level is None or not np.isfinite(float(level)):
             raise lib.MofaError(f"extract_mesh: level must be a finite number (got {level})")
         if colors and uvCodes is None:
@@ -1136,13 +1145,18 @@ class Renderer(torch.nn.Module):
             grid = self.query_density(network, bounds=bounds, resolution=resolution, shapeCodes=shapeCodes, expType=expType,
                                       expCodes=expCodes, netchunk=netchunk)
         with torch.no_grad():
-            if brick is None and not extra:
+            if brick is None and not extra and components is None:
                 verts, faces = mesh.iso_surface(grid, float(level), lo, step)
             elif brick is None:
                 verts, faces, edge_ids = mesh.iso_surface(grid, float(level), lo, step, edge_ids=True)
                 self.mesh_stats = {"edge_ids": edge_ids}
             else:
                 verts, faces = self._band_mesh(network, res, lo, step, float(level), int(brick), shapeCodes, expType, expCodes, netchunk)
+            if components is not None:
+                stats = mesh.components(verts, faces)
+                stats["kept"] = mesh.select_components(stats, components)
+                verts, faces, self.mesh_stats["edge_ids"] = mesh.keep_components(verts, faces, stats, stats["kept"], self.mesh_stats["edge_ids"])
+                self.mesh_stats["components"] = stats
             nrm = None
             if extra:
                 verts, nrm = self._refine_mesh(network, verts, faces, res, lo, step, float(level), refine, normals, shapeCodes, expType,

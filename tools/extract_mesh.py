@@ -19,6 +19,11 @@ meshes are equal after renumbering by edge id:
 ``--refine K`` then moves every vertex along its lattice edge onto the level by K bisection steps on the network's density (the
 placement of a grid 2^K times finer along each edge; faces unchanged), and ``--normals density|faces`` writes per-vertex normals
 (``nx ny nz``) to the PLY.
+
+``--components largest`` or ``--components N`` removes floaters before any of that: the mesh's connected components are labelled on the
+GPU and only the one with the most faces, or every one with at least N faces, is kept; the tool prints the largest components (faces,
+area, signed volume, box) and what was removed.  With ``--time`` it also prints the labelling's passes and the time of each stage next to
+the extraction's.  ON SEEDED WEIGHTS THE COMPONENTS SAY NOTHING ABOUT THE FLOATERS OF A TRAINED FACE: a seeded network's density is noise.
 """
 import argparse
 import itertools
@@ -58,6 +63,34 @@ def load(a, dev):
     return render, net, bm.reshape(1, -1).float().to(dev), uv.reshape(-1).float().to(dev), exp.reshape(1, -1).float().to(dev)
 
 
+def components_arg(text):
+    if text == "largest":
+        return text
+    try:
+        n = int(text)
+    except ValueError:
+        n = 0
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"{text!r}: want 'largest' or a face count >= 1")
+    return n
+
+
+def components_report(st, top=8):
+    """The largest components of the unfiltered mesh and what the filter removed (render.mesh_stats["components"])."""
+    n_c = st["n_components"]
+    n_faces, n_verts, kept = st["n_faces"].cpu(), st["n_verts"].cpu(), st["kept"].cpu()
+    area, volume, bbox = st["area"].cpu(), st["volume"].cpu(), st["bbox"].cpu()
+    print(f"components: {n_c} over {int(n_faces.sum())} faces, labelled in {st['passes']} passes; {st['unreferenced']} unreferenced vertices")
+    print("  label      faces      verts          area        volume  kept  box")
+    for c in torch.argsort(n_faces, descending=True, stable=True)[:top].tolist():
+        lo, hi = bbox[c, 0].tolist(), bbox[c, 1].tolist()
+        box = " ".join(f"[{a:.3f}, {b:.3f}]" for a, b in zip(lo, hi))
+        print(f"  {c:5d} {int(n_faces[c]):10d} {int(n_verts[c]):10d} {float(area[c]):13.6g} {float(volume[c]):13.6g}  {'yes' if kept[c] else 'no ':4s} {box}")
+    gone = ~kept
+    print(f"removed {int(gone.sum())} components: {int(n_faces[gone].sum())} faces, {int(n_verts[gone].sum())} vertices, area "
+          f"{float(area[gone].sum()):.6g}, volume {float(volume[gone].sum()):.6g}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     src = ap.add_mutually_exclusive_group(required=True)
@@ -79,7 +112,11 @@ def main(argv=None):
                     "bisection steps on the density (0 .. 20; (2 + K) V more density evaluations, faces unchanged)")
     ap.add_argument("--normals", choices=("density", "faces"), default=None, help="write per-vertex normals to the PLY: the density "
                     "field's (central differences at half a grid step) or the area-weighted face normals")
+    ap.add_argument("--components", type=components_arg, default=None, metavar="largest|N", help="remove floaters: keep the connected "
+                    "component with the most faces, or every component with at least N faces (before --refine / --normals / --colors)")
     a = ap.parse_args(argv)
+    if a.compare_dense and a.components is not None:
+        ap.error("--compare-dense compares the unfiltered meshes: drop --components")
     if a.compare_dense and a.brick is None:
         ap.error("--compare-dense needs --brick")
     if a.compare_dense and a.refine:
@@ -90,10 +127,14 @@ def main(argv=None):
     res = tuple(a.resolution)
     kw = dict(bounds=bounds, resolution=res, shapeCodes=bm, expType=20, expCodes=exp, netchunk=a.netchunk)
     out = render.extract_mesh(net, level=a.level, uvCodes=uv if a.colors else None, colors=a.colors, brick=a.brick, refine=a.refine,
-                              normals=a.normals, **kw)
+                              normals=a.normals, components=a.components, **kw)
     verts, faces = out[0], out[1]
     mesh.write_ply(a.out, verts, faces, out[2] if a.colors else None, normals=out[-1] if a.normals else None)
     print(f"wrote {a.out}: V = {verts.shape[0]}, F = {faces.shape[0]}")
+    if a.components is not None:
+        if a.synthetic:
+            print("seeded synthetic weights: the components below say NOTHING about the floaters of a trained face")
+        components_report(render.mesh_stats["components"])
     if a.refine:
         print(f"refined by {a.refine} bisection steps: {render.mesh_stats['refine']['evaluations']} density evaluations at the vertices' edges")
     if a.normals == "density":
@@ -139,6 +180,16 @@ def main(argv=None):
     print(f"density speed-up over the full forward: {t_full / t_density:.3f}x  (bit-identical sigma)")
     print(f"extraction (count + read + emit): {t_iso * 1e3:9.3f} ms  = {100 * t_iso / t_density:.3f} % of the density query")
     print(f"V = {v2.shape[0]}, F = {f2.shape[0]}")
+    if a.components is not None:
+        ids = torch.arange(v2.shape[0], device=dev)
+        t_cc, st = timed(lambda: mesh.components(v2, f2))
+        _, st_t = timed(lambda: mesh.components(v2, f2, timing=True), reps=1)
+        mask = mesh.select_components(st, a.components)
+        t_keep, kept = timed(lambda: mesh.keep_components(v2, f2, st, mask, ids))
+        phases = ", ".join(f"{k} {v * 1e3:.3f}" for k, v in st_t["times"].items())
+        print(f"components: {st['n_components']} in {st['passes']} passes, {t_cc * 1e3:9.3f} ms = {100 * t_cc / t_iso:.1f} % of the extraction "
+              f"(phases, each ended by a synchronisation, ms: {phases})")
+        print(f"compaction to {kept[0].shape[0]} vertices / {kept[1].shape[0]} faces with one companion: {t_keep * 1e3:9.3f} ms")
 
 
 def renumbered(verts, faces, edge_ids):

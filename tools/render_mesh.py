@@ -8,7 +8,8 @@ volume's depth are the same quantity: the ray parameter of the pixel's ``get_ray
 Writes ``level_<level>_mesh.png`` (head-light shade) and ``level_<level>_mesh_depth.png`` per level and ``volume_depth.png`` into
 ``--out``; prints one JSON line at the end.  ``--refine K`` extracts every level a second time with its vertices moved onto the level by
 K bisection steps along their lattice edges (``extract_mesh(refine=K)``) and prints the agreement without and with: the difference is
-what the linear vertex placement contributed to the first number.
+what the linear vertex placement contributed to the first number.  ``--components largest|N`` is passed to ``extract_mesh``: floaters
+are removed before the mesh is rasterised, so a level's agreement can be read with and without them.
 
 Networks come from a checkpoint (``--ckpt``) or seeded synthetic weights (``--synthetic DC WC DF WF``), codes from ``--fit`` or
 ``synth.codes`` — the options of tools/render_geometry.py.  ON SEEDED WEIGHTS THE AGREEMENT NUMBERS MEAN NOTHING ABOUT A TRAINED FACE:
@@ -29,6 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mofanerf_amd import mesh, synth  # noqa: E402
 from mofanerf_amd.io import PngSink  # noqa: E402
 from mofanerf_amd.rays import pose_spherical  # noqa: E402
+from extract_mesh import components_arg  # noqa: E402
 from render_culled import load  # noqa: E402
 
 
@@ -61,6 +63,8 @@ def main(argv=None):
     lv.add_argument("--levels", help="several, comma-separated: a,b,c")
     ap.add_argument("--refine", type=int, default=0, metavar="K", help="also extract every level with its vertices moved onto the level by K "
                     "bisection steps along their edges (extract_mesh(refine=K)); the agreement is printed without and with")
+    ap.add_argument("--components", type=components_arg, default=None, metavar="largest|N", help="remove floaters before rasterising: "
+                    "extract_mesh(components=...) keeps the component with the most faces, or every one with at least N faces")
     ap.add_argument("--size", type=int, default=512, help="frame height = width")
     ap.add_argument("--samples", type=int, nargs=2, default=[64, 128], metavar=("N_SAMPLES", "N_IMPORTANCE"))
     ap.add_argument("--near", type=float, default=8.0)
@@ -108,7 +112,7 @@ def main(argv=None):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 verts, faces = render.extract_mesh(net, bounds=bounds, resolution=tuple(a.resolution), level=level, shapeCodes=bm, expType=20,
-                                                   expCodes=exp, netchunk=a.netchunk, brick=a.brick, refine=k)[:2]
+                                                   expCodes=exp, netchunk=a.netchunk, brick=a.brick, refine=k, components=a.components)[:2]
                 torch.cuda.synchronize()
                 t_extract = (time.perf_counter() - t0) * 1e3
                 t_mesh, all_mesh, (rgb, depth, mask, mex) = median_ms(
@@ -116,6 +120,10 @@ def main(argv=None):
                 t_raster, _, _ = median_ms(lambda: mesh.rasterize(verts, faces, H, H, K, pose, znear=a.znear), a.warmup, a.frames)
                 agree = mesh.depth_agreement(depth, mask, depth_vol, acc, a.acc_min)
                 drawn, culled, degenerate, wave = (int(v) for v in mex["counts"].cpu())
+                if a.components is not None:
+                    cs = render.mesh_stats["components"]
+                    print(f"  components={a.components}: kept {int(cs['kept'].sum())} of {cs['n_components']} components, "
+                          f"{int(faces.shape[0])} of {int(cs['n_faces'].sum())} faces ({cs['passes']} passes)", flush=True)
                 row = {"level": level, "refine": k, "V": int(verts.shape[0]), "F": int(faces.shape[0]), "extract_ms": round(t_extract, 2), "render_mesh_ms": t_mesh,
                        "render_mesh_ms_all": all_mesh, "rasterize_ms": t_raster, "faces_drawn": drawn, "faces_culled": culled,
                        "faces_degenerate": degenerate, "faces_wave_path": wave, **agree}
@@ -130,7 +138,7 @@ def main(argv=None):
                 sink.submit(stem + "_mesh.png", rgb)
                 sink.submit(stem + "_mesh_depth.png", (((depth - a.near) / span) * mask)[..., None].expand(H, H, 3))
     print(json.dumps({"size": H, "samples": a.samples, "angle": a.angle, "radius": a.radius, "near": a.near, "far": a.far, "acc_min": a.acc_min,
-                      "median_threshold": a.median_threshold, "resolution": a.resolution, "brick": a.brick, "refine": a.refine,
+                      "median_threshold": a.median_threshold, "resolution": a.resolution, "brick": a.brick, "refine": a.refine, "components": a.components,
                       "wave_min_pixels": mesh.WAVE_MIN_PIXELS, "synthetic_weights": bool(a.synthetic),
                       "agreement_says_nothing_about_a_trained_face": bool(a.synthetic), "render_geometry_ms": t_vol,
                       "render_geometry_ms_all": all_vol, "levels": rows, "out": a.out}))
