@@ -344,6 +344,46 @@ int mofa_cc_seg_minmax(const float* in, int32_t boxes, const int64_t* perm, int6
                        int64_t n_segments, int64_t longest, float* out, void* stream);
 int mofa_cc_remap(const int32_t* in, int64_t n, const int32_t* vmap, int64_t V, int32_t* out, void* stream);
 
+/* Mesh simplification: vertex clustering on a lattice of cells, one quadric-error representative per cluster (mesh.py drives the passes:
+ * mesh.simplify; 1 <= V, F, C <= 2^31 - 1, anything indexed by 3 F is 64-bit).  No float or double atomics: sums are fixed-order, fixed-tree
+ * segmented reductions, so the same mesh gives the same bits every time; the only atomics are the integer counters counts[MOFA_SIMP_COUNTS]
+ * (int64, DEVICE, zeroed by the caller).  Every kernel checks the indices it dereferences: a bad one is counted in
+ * counts[MOFA_SIMP_BAD_INDEX] and skipped.  No kernel waits on another thread.  All arithmetic has every operation rounded separately.
+ *   mofa_simp_keys             keys[v] (int64) = (q_x << 42) | (q_y << 21) | q_z with q_a = floorf((x_a - origin_a) / cell_a) in fp32; a vertex
+ *                              with a non-finite coordinate or a q_a outside [0, 2^21) gets -1 and is counted in counts[MOFA_SIMP_BAD_VERTEX]
+ *   mofa_simp_corner_quadrics  quadrics [F,10] (double), from the fp32 coordinates in fp64: n = (v1 - v0) x (v2 - v0) (un-normalised: area^2
+ *                              weights), d = -((nx v0x + ny v0y) + nz v0z), row = nx nx, nx ny, nx nz, ny ny, ny nz, nz nz, nx d, ny d, nz d, d d.
+ *                              The quadric of face f belongs to the cluster of each of its corners: pair 3 f + c.  The 3 F pairs are not
+ *                              materialised; mofa_simp_seg_sum gathers row perm[i] / 3 (80 F bytes instead of 240 F).
+ *   mofa_simp_seg_sum          out [n_segments, ncols] (double; ncols = 4 or 10): out[s] = the sum over i in [seg_start[s], seg_end[s]) of row
+ *                              perm[i] / row_div of in [N, ncols] (perm int64 [N row_div], DEVICE; NULL = the identity, row_div = 1): one
+ *                              workgroup per segment, thread t adds i = s0 + t, s0 + t + 256, ... in that order from +0.0, then the tree
+ *                              sm[t] += sm[t + w] (t < w) for w = 128, 64, ..., 1.  longest >= every segment's length.
+ *   mofa_simp_place            out [C,3] (float), one representative per cluster from its summed quadric Q [C,10] and S [C,4] = the sum of
+ *                              (x, y, z, 1) over its vertices, in fp64 in this order:
+ *                                m_a = S_a / S_3;  w = regularize ((Q0 + Q3) + Q5);  a00 = Q0 + w, a11 = Q3 + w, a22 = Q5 + w, a01 = Q1, a02 = Q2,
+ *                                a12 = Q4;  r_a = w m_a - Q(6 + a);  c00 = a11 a22 - a12 a12, c01 = a02 a12 - a01 a22, c02 = a01 a12 - a02 a11,
+ *                                c11 = a00 a22 - a02 a02, c12 = a01 a02 - a00 a12, c22 = a00 a11 - a01 a01;  det = (a00 c00 + a01 c01) + a02 c02;
+ *                                x_0 = ((c00 r0 + c01 r1) + c02 r2) / det, x_1 = ((c01 r0 + c11 r1) + c12 r2) / det, x_2 = ((c02 r0 + c12 r1) + c22 r2) / det
+ *                              (float) x is taken iff w > 0, w and det finite, det > 0 and mofa_simp_keys' arithmetic on it gives cluster_keys[c];
+ *                              otherwise (float) m under the same key test; otherwise verts[first[c]].  mode MOFA_SIMP_PLACE_MEAN starts at
+ *                              the mean (quadrics may be NULL).  counts[MOFA_SIMP_QUADRIC / _MEAN / _FIRST] += the route taken,
+ *                              counts[MOFA_SIMP_MEAN_REQUESTED] += the clusters asked to start at the mean.
+ *   mofa_simp_faces            out[f] = (cluster[faces[f][c]])_c rotated so that the smallest index comes first (orientation kept);
+ *                              degenerate[f] (uint8) = two of the three are equal, or an index was bad (then out[f] = -1 -1 -1) */
+enum { MOFA_SIMP_BAD_VERTEX = 0, MOFA_SIMP_QUADRIC = 1, MOFA_SIMP_MEAN = 2, MOFA_SIMP_FIRST = 3, MOFA_SIMP_MEAN_REQUESTED = 4,
+       MOFA_SIMP_BAD_INDEX = 5, MOFA_SIMP_COUNTS = 6 };
+enum { MOFA_SIMP_PLACE_QUADRIC = 0, MOFA_SIMP_PLACE_MEAN = 1 };
+int mofa_simp_keys(const float* verts, int64_t V, const float origin[3], const float cell[3], int64_t* keys, int64_t* counts, void* stream);
+int mofa_simp_corner_quadrics(const float* verts, const int32_t* faces, int64_t F, int64_t V, double* quadrics, int64_t* counts, void* stream);
+int mofa_simp_seg_sum(const double* in, int32_t ncols, const int64_t* perm, int32_t row_div, int64_t N, const int64_t* seg_start,
+                      const int64_t* seg_end, int64_t n_segments, int64_t longest, double* out, void* stream);
+int mofa_simp_place(const double* quadrics, const double* vsum, const int64_t* cluster_keys, const int32_t* first, const float* verts, int64_t V,
+                    int64_t C, const float origin[3], const float cell[3], double regularize, int32_t mode, float* out, int64_t* counts,
+                    void* stream);
+int mofa_simp_faces(const int32_t* faces, int64_t F, int64_t V, const int32_t* cluster, int64_t C, int32_t* out, uint8_t* degenerate,
+                    int64_t* counts, void* stream);
+
 /* ---- occupancy-culled rendering: skip the network where an occupancy grid says the space is empty ---------------------------------
  * The grid lives on the lattice of mofa_grid_points (nx x ny x nz samples at lo + (i,j,k) step): (nx-1)(ny-1)(nz-1) cells, one byte
  * each (0 / 1), cell index (i (ny-1) + j) (nz-1) + k.  The lattice needs 2 <= n < 2^24 per axis and fewer than 2^31 cells.

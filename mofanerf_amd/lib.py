@@ -86,6 +86,12 @@ SIGNATURES = {
     "mofa_cc_seg_sum": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _i64, _i64, _fp, _fp]),
     "mofa_cc_seg_minmax": (C.c_int, [_fp, _i32, _fp, _i64, _fp, _fp, _i64, _i64, _fp, _fp]),
     "mofa_cc_remap": (C.c_int, [_fp, _i64, _fp, _i64, _fp, _fp]),
+    "mofa_simp_keys": (C.c_int, [_fp, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), _fp, _fp, _fp]),
+    "mofa_simp_corner_quadrics": (C.c_int, [_fp, _fp, _i64, _i64, _fp, _fp, _fp]),
+    "mofa_simp_seg_sum": (C.c_int, [_fp, _i32, _fp, _i32, _i64, _fp, _fp, _i64, _i64, _fp, _fp]),
+    "mofa_simp_place": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i64, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_double, _i32, _fp, _fp,
+                                  _fp]),
+    "mofa_simp_faces": (C.c_int, [_fp, _i64, _i64, _fp, _i64, _fp, _fp, _fp, _fp]),
     "mofa_occ_workspace_bytes": (_sz, [_i64]),
     "mofa_occ_cells": (C.c_int, [_fp, _i64, _i64, _i64, C.c_float, _i32, _fp, _fp]),
     "mofa_occ_dilate": (C.c_int, [_fp, _i64, _i64, _i64, _i32, _fp, _fp, _fp]),

@@ -545,6 +545,194 @@ def keep_components(verts: torch.Tensor, faces: torch.Tensor, stats: dict, mask:
         return (verts[vkeep], new) + tuple(p[vkeep] for p in per_vertex)
 
 
+SIMP_MAX_CELLS = 2 ** 21                     # cells per axis a key can hold
+_SIMP_COUNTS = ("bad_vertex", "placed_quadric", "placed_mean", "placed_first", "mean_requested", "bad_index")      # MOFA_SIMP_* of the header
+_SIMP_PLACEMENTS = {"quadric": 0, "mean": 1}                                                                   # MOFA_SIMP_PLACE_*
+
+
+def _simp_two_level(L, rows, ncols, perm, row_div, counts, offset, stream):
+    """[C, ncols] float64: per label, the sum of its run of ``perm`` (elements sorted by label, ``counts [C]`` per label, the first run at
+    ``offset``) over rows ``perm // row_div`` of ``rows [N, ncols]``: chunks of CC_CHUNK first, then each label's chunks
+    (``mofa_simp_seg_sum`` twice: a fixed order and a fixed tree at both levels)."""
+    run, first, per_label = _cc_runs(counts, offset)
+    n_chunks, most = (int(v) for v in torch.stack([first[-1], per_label.max()]).cpu())
+    start, end = _cc_chunks(run, first, per_label, n_chunks)
+    partial = torch.empty(n_chunks, ncols, dtype=torch.float64, device=rows.device)
+    lib.check(L.mofa_simp_seg_sum(rows.data_ptr(), ncols, perm.data_ptr(), row_div, rows.shape[0], start.data_ptr(), end.data_ptr(), n_chunks,
+                                  CC_CHUNK, partial.data_ptr(), stream), "mofa_simp_seg_sum")
+    out = torch.empty(counts.shape[0], ncols, dtype=torch.float64, device=rows.device)
+    start, end = first[:-1].contiguous(), first[1:].contiguous()
+    lib.check(L.mofa_simp_seg_sum(partial.data_ptr(), ncols, None, 1, n_chunks, start.data_ptr(), end.data_ptr(), counts.shape[0], most,
+                                  out.data_ptr(), stream), "mofa_simp_seg_sum")
+    return out
+
+
+def _dense_ids(key):
+    """Rank of every int64 key among the distinct keys (ascending), and how many there are, as a tensor."""
+    uniq, inverse = torch.unique(key, sorted=True, return_inverse=True)
+    return inverse, uniq.shape[0]
+
+
+def simplify(verts: torch.Tensor, faces: torch.Tensor, cell, origin=None, regularize: float = 1e-3, placement: str = "quadric",
+             timing: bool = False):
+    """Simplify a triangle mesh on the GPU by vertex clustering with one quadric-error representative per cluster (``mofa_simp_*``;
+    Rossignac-Borrel clustering, Lindstrom's placement).  ``cell`` (a float or three) is the cell size, ``origin`` the lattice's corner
+    (default: the per-axis minimum of ``verts``).  Every vertex some face references falls into the cell ``floorf((x - origin) / cell)``
+    (fp32); the clusters are the occupied cells, numbered by ascending key ``(q_x << 42) | (q_y << 21) | q_z``.  Each cluster sums, in
+    fp64 and in a fixed order, the quadrics of the faces at its corners (un-normalised normals: area^2 weights; a face with two corners in
+    a cluster counts twice there) and places its representative at the minimiser of that quadric plus ``w |x - mean|^2``,
+    ``w = regularize * trace(A)``: the regularisation pulls the directions a flat or straight patch leaves free toward the cluster's
+    mean and bounds the condition number by about ``1 / regularize``.  The representative is rounded to fp32 and must lie in its own cell
+    (the key arithmetic on it gives the cluster's key); otherwise the mean is taken under the same test, otherwise the cluster's
+    lowest-index vertex.  ``placement="mean"`` skips the solve: plain vertex clustering, the baseline.
+
+    Faces are rewritten to cluster indices; a face with two equal indices is dropped, and among the faces with one vertex set, with p and
+    q faces of the two orientations, the first ``|p - q|`` of the majority orientation are kept in face order ("fins" cancel).  That rule
+    keeps ``count(a -> b) - count(b -> a)`` of every directed edge, so a closed, consistently oriented input gives a closed, consistently
+    oriented output in that sense.  The output may be non-manifold and may intersect itself, as with every clustering method.  Clusters no
+    kept face uses are dropped; kept vertices come in ascending key order, faces in their old order, each rotated so that its smallest
+    index comes first.  No float atomics: the same mesh gives the same bytes every time.
+
+    Returns ``(verts' [V',3] float32, faces' [F',3] int32, stats)``; ``stats``: ``n_clusters``, ``verts_in``, ``faces_in``, ``verts_out``,
+    ``faces_out``, ``faces_degenerate``, ``faces_cancelled``, ``placed_quadric`` / ``placed_mean`` / ``placed_first`` (the route of every
+    cluster), ``mean_requested``, ``edges_multiple`` (directed edges of the output more than one face uses), ``cluster_of [V] int32`` (the
+    output vertex each input vertex went to, -1 if dropped) and, with ``timing=True``, ``times`` (seconds of the ``validate``, ``keys``,
+    ``clusters``, ``sums``, ``place``, ``faces`` and ``compact`` phases, each ended by a device synchronisation).
+
+    A face index outside the mesh raises ``MofaError`` after ``mofa_cc_validate`` and before any other kernel; a vertex that is not finite
+    or lies outside the 2^21 cells per axis raises it after ``mofa_simp_keys``; so do CPU tensors and a ``cell`` or ``regularize`` that is
+    not finite and positive.  ``V == 0`` or ``F == 0`` returns empty tensors without a launch.  What the method does to a trained face,
+    and whether 1e-3 is the right ``regularize``, has not been measured."""
+    who = "simplify"
+    V, F, dev = _mesh_tensors(who, verts, faces)
+    cell3 = np.asarray(cell, dtype=np.float32).reshape(-1)
+    if cell3.size not in (1, 3) or not (np.isfinite(cell3).all() and (cell3 > 0).all()):
+        raise lib.MofaError(f"{who}: cell = {cell} (want one or three finite sizes > 0)")
+    cell3 = np.repeat(cell3, 3) if cell3.size == 1 else cell3
+    regularize = float(regularize)
+    if not (np.isfinite(regularize) and regularize > 0):
+        raise lib.MofaError(f"{who}: regularize = {regularize} (want finite and > 0: the flat patches of any real mesh make A singular)")
+    if placement not in _SIMP_PLACEMENTS:
+        raise lib.MofaError(f"{who}: placement = {placement!r} (want 'quadric' or 'mean')")
+    i64 = dict(dtype=torch.int64, device=dev)
+    if V == 0 or F == 0:
+        stats = dict.fromkeys(("n_clusters", "verts_out", "faces_out", "faces_degenerate", "faces_cancelled", "placed_quadric", "placed_mean",
+                               "placed_first", "mean_requested", "edges_multiple"), 0)
+        stats.update(verts_in=V, faces_in=F, cluster_of=torch.full((V,), -1, dtype=torch.int32, device=dev))
+        return verts[:0], faces[:0], stats
+    L = lib.load()
+    times, clock = {}, [time.perf_counter()]
+
+    def lap(phase):
+        if timing:
+            torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            times[phase] = now - clock[0]
+            clock[0] = now
+
+    with torch.cuda.device(dev):
+        stream = lib.stream()
+        lap("start")
+        bad = torch.zeros(1, **i64)
+        lib.check(L.mofa_cc_validate(faces.data_ptr(), F, V, bad.data_ptr(), stream), "mofa_cc_validate")
+        n_bad = int(bad.cpu()[0])
+        if n_bad:
+            raise lib.MofaError(f"{who}: {n_bad} of the {3 * F} face indices lie outside [0, {V})")
+        lap("validate")
+        org3 = verts.amin(0).cpu().numpy() if origin is None else np.asarray(origin, dtype=np.float32).reshape(-1)
+        if org3.size != 3 or not np.isfinite(org3).all():
+            raise lib.MofaError(f"{who}: origin = {org3.tolist()} (want three finite coordinates; the default is the vertices' minimum)")
+        o3, c3 = _f3(org3), _f3(cell3)
+        counts = torch.zeros(len(_SIMP_COUNTS), **i64)
+        key = torch.empty(V, **i64)
+        lib.check(L.mofa_simp_keys(lib.ptr(verts), V, o3, c3, key.data_ptr(), counts.data_ptr(), stream), "mofa_simp_keys")
+        n_bad = int(counts.cpu()[0])
+        if n_bad:
+            raise lib.MofaError(f"{who}: {n_bad} of the {V} vertices are not finite or lie outside the {SIMP_MAX_CELLS} cells per axis from "
+                                f"origin {org3.tolist()} with cell {cell3.tolist()}")
+        lap("keys")
+        # clusters: the occupied cells of the referenced vertices, numbered by ascending key
+        flat = faces.reshape(-1).long()
+        referenced = torch.zeros(V, dtype=torch.bool, device=dev)
+        referenced[flat] = True
+        cluster_keys, inverse = torch.unique(key[referenced], sorted=True, return_inverse=True)
+        n_c = int(cluster_keys.shape[0])
+        cluster = torch.full((V,), -1, **i64)
+        cluster[referenced] = inverse
+        cluster32 = cluster.to(torch.int32)
+        lap("clusters")
+        # sums: (x, y, z, 1) over each cluster's vertices and the quadrics over its corners, both stably sorted by cluster
+        order = torch.sort(cluster, stable=True).indices                              # (the unreferenced -1 come first)
+        n_verts = torch.bincount(inverse, minlength=n_c)
+        n_ref = int(inverse.shape[0])
+        rows = torch.cat([verts.double(), torch.ones(V, 1, dtype=torch.float64, device=dev)], 1).contiguous()
+        vsum = _simp_two_level(L, rows, 4, order, 1, n_verts, V - n_ref, stream)
+        first = order[(V - n_ref) + torch.cumsum(n_verts, 0) - n_verts].to(torch.int32)       # a stable sort: each run starts at its lowest index
+        qsum = None
+        if placement == "quadric":
+            quadrics = torch.empty(F, 10, dtype=torch.float64, device=dev)
+            lib.check(L.mofa_simp_corner_quadrics(lib.ptr(verts), faces.data_ptr(), F, V, quadrics.data_ptr(), counts.data_ptr(), stream),
+                      "mofa_simp_corner_quadrics")
+            corner = cluster[flat]
+            perm = torch.sort(corner, stable=True).indices
+            qsum = _simp_two_level(L, quadrics, 10, perm, 3, torch.bincount(corner, minlength=n_c), 0, stream)
+            del quadrics, perm, corner
+        lap("sums")
+        rep = torch.empty(n_c, 3, dtype=torch.float32, device=dev)
+        lib.check(L.mofa_simp_place(None if qsum is None else qsum.data_ptr(), vsum.data_ptr(), cluster_keys.data_ptr(), first.data_ptr(),
+                                    lib.ptr(verts), V, n_c, o3, c3, regularize, _SIMP_PLACEMENTS[placement], lib.ptr(rep), counts.data_ptr(),
+                                    stream), "mofa_simp_place")
+        lap("place")
+        # faces: cluster indices in canonical rotation; degenerate faces go, fins cancel
+        rot = torch.empty(F, 3, dtype=torch.int32, device=dev)
+        degenerate = torch.empty(F, dtype=torch.uint8, device=dev)
+        lib.check(L.mofa_simp_faces(faces.data_ptr(), F, V, cluster32.data_ptr(), n_c, rot.data_ptr(), degenerate.data_ptr(), counts.data_ptr(),
+                                    stream), "mofa_simp_faces")
+        alive = torch.nonzero(degenerate == 0)[:, 0]
+        tri = rot[alive].long()
+        n_alive = int(tri.shape[0])
+        keep = torch.ones(n_alive, dtype=torch.bool, device=dev)
+        if n_alive:
+            lo, hi = torch.minimum(tri[:, 1], tri[:, 2]), torch.maximum(tri[:, 1], tri[:, 2])
+            pair, _ = _dense_ids(tri[:, 0] * (1 << 31) + lo)                         # (indices < 2^31: the products fit 62 bits)
+            group, n_groups = _dense_ids(pair * (1 << 31) + hi)
+            k = 2 * group + (tri[:, 1] > tri[:, 2]).long()                           # the vertex set and the orientation
+            by_k = torch.sort(k, stable=True).indices
+            count = torch.bincount(k, minlength=2 * n_groups)
+            begin = torch.cumsum(count, 0) - count
+            rank = torch.empty(n_alive, **i64)
+            rank[by_k] = torch.arange(n_alive, **i64) - begin[k[by_k]]
+            keep = rank < count[k] - count[k ^ 1]
+        kept = rot[alive[keep]].contiguous()
+        lap("faces")
+        # compaction: the clusters a kept face uses, in key order
+        used = torch.zeros(n_c, dtype=torch.bool, device=dev)
+        used[kept.reshape(-1).long()] = True
+        vmap = torch.where(used, torch.cumsum(used, 0, dtype=torch.int32) - 1, -1).to(torch.int32)
+        out_f = torch.empty_like(kept)
+        if kept.numel():
+            lib.check(L.mofa_cc_remap(kept.data_ptr(), kept.numel(), vmap.data_ptr(), n_c, out_f.data_ptr(), stream), "mofa_cc_remap")
+        out_v = rep[used]
+        cluster_of = torch.where(referenced, vmap[cluster.clamp(min=0)], -1).to(torch.int32)
+        multiple = 0
+        if out_f.shape[0]:
+            f2 = out_f.long()
+            edges = torch.cat([f2[:, 0] * (1 << 31) + f2[:, 1], f2[:, 1] * (1 << 31) + f2[:, 2], f2[:, 2] * (1 << 31) + f2[:, 0]])
+            multiple = (torch.unique(edges, return_counts=True)[1] > 1).sum()
+        c = dict(zip(_SIMP_COUNTS, (int(v) for v in counts.cpu())))                  # the counters, read once
+        lap("compact")
+    if c["bad_index"]:
+        raise lib.MofaError(f"{who}: {c['bad_index']} indices were out of range inside the passes (the mesh changed while it was simplified?)")
+    stats = {"n_clusters": n_c, "verts_in": V, "faces_in": F, "verts_out": int(out_v.shape[0]), "faces_out": int(out_f.shape[0]),
+             "faces_degenerate": F - n_alive, "faces_cancelled": n_alive - int(kept.shape[0]), "placed_quadric": c["placed_quadric"],
+             "placed_mean": c["placed_mean"], "placed_first": c["placed_first"], "mean_requested": c["mean_requested"],
+             "edges_multiple": int(multiple), "cluster_of": cluster_of}
+    if timing:
+        times.pop("start")
+        stats["times"] = times
+    return out_v, out_f, stats
+
+
 # faces whose clipped box of samples holds at least this many pixels are walked one wavefront per face (mofa_raster_faces); the choice
 # changes no bit of the frame.  profiles/mesh_raster.md holds the sweep it comes from.
 WAVE_MIN_PIXELS = 64
@@ -725,5 +913,5 @@ def read_ply(path: str):
     return verts, faces, colors, np.stack([vrec["nx"], vrec["ny"], vrec["nz"]], -1).astype(np.float32).reshape(-1, 3)
 
 
-__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "refine_vertices", "density_normals", "vertex_normals", "components", "select_components", "keep_components", "rasterize", "depth_agreement", "to8b", "write_ply",
+__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "refine_vertices", "density_normals", "vertex_normals", "components", "select_components", "keep_components", "simplify", "rasterize", "depth_agreement", "to8b", "write_ply",
                            "read_ply")

@@ -1097,7 +1097,7 @@ class Renderer(torch.nn.Module):
             return occupancy.occupancy_from_grids(grids, threshold, lo, step, dilate)
 
     def extract_mesh(self, network, *, bounds, resolution, level, shapeCodes, expType=20, expCodes=None, uvCodes=None, colors=False,
-                     netchunk=None, brick=None, refine=0, normals=None, components=None):
+                     netchunk=None, brick=None, refine=0, normals=None, components=None, simplify=None, placement="quadric"):
         """Triangle mesh of the face: ``{density >= level}`` over the grid of :meth:`query_density`, by marching tetrahedra on the GPU
         (``mofa_iso_count`` / ``mofa_iso_emit``).  Returns ``(verts [V,3] float32, faces [F,3] int32)`` — watertight, normals
         ``(v1 - v0) x (v2 - v0)`` toward lower density — plus, with ``colors=True`` (needs ``uvCodes``), ``colors [V,3]`` in [0,1]:
@@ -1125,8 +1125,21 @@ class Renderer(torch.nn.Module):
         (which then run on the kept vertices only): the mesh's connected components are labelled (``mesh.components``) and only the one
         with the most faces, or every one with at least ``n`` faces, is kept (``mesh.keep_components``; kept vertices and faces stay in
         their order).  ``self.mesh_stats["components"]`` then holds the statistics of the unfiltered mesh plus ``kept`` (the mask), and
-        ``self.mesh_stats["edge_ids"]`` is filtered with the vertices.  ``None`` launches nothing and returns the same bytes as before."""
+        ``self.mesh_stats["edge_ids"]`` is filtered with the vertices.  ``None`` launches nothing and returns the same bytes as before.
+
+        ``simplify=m`` (an integer >= 2) simplifies the mesh by vertex clustering with quadric-error representatives (``mesh.simplify``) on
+        cells of ``m`` grid steps per axis from the grid's ``lo``, so the clusters are lattice-aligned; ``placement="mean"`` is the plain
+        clustering baseline.  It runs after ``components=`` and ``refine=`` (refinement needs the edge ids, which do not survive: the
+        ``edge_ids`` entry of ``self.mesh_stats`` is dropped) and before ``normals=`` and ``colors=``, which are network evaluations at
+        vertex positions and so run on the fewer vertices (``self.mesh_stats["normal_evaluations"]`` / ``["color_evaluations"]`` count
+        them); ``normals="faces"`` is computed on the simplified mesh.  ``self.mesh_stats["simplify"]`` keeps ``mesh.simplify``'s
+        statistics.  The result is closed where the input is, but not necessarily manifold.  ``None`` launches nothing and returns the
+        same bytes as before.  What it does to a trained face has not been measured."""
         from . import mesh
+        if simplify is not None and not (isinstance(simplify, (int, np.integer)) and not isinstance(simplify, (bool, np.bool_)) and simplify >= 2):
+            raise lib.MofaError(f"extract_mesh: simplify = {simplify!r} (want None or an integer >= 2: grid steps per cell)")
+        if placement not in ("quadric", "mean"):
+            raise lib.MofaError(f"extract_mesh: placement = {placement!r} (want 'quadric' or 'mean')")
         if components is not None and components != "largest" and not (isinstance(components, (int, np.integer)) and
                                                                        not isinstance(components, (bool, np.bool_)) and components >= 1):
             raise lib.MofaError(f"extract_mesh: components = {components!r} (want None, 'largest' or a face count >= 1)")
@@ -1145,7 +1158,7 @@ class Renderer(torch.nn.Module):
             grid = self.query_density(network, bounds=bounds, resolution=resolution, shapeCodes=shapeCodes, expType=expType,
                                       expCodes=expCodes, netchunk=netchunk)
         with torch.no_grad():
-            if brick is None and not extra and components is None:
+            if brick is None and not extra and components is None and simplify is None:
                 verts, faces = mesh.iso_surface(grid, float(level), lo, step)
             elif brick is None:
                 verts, faces, edge_ids = mesh.iso_surface(grid, float(level), lo, step, edge_ids=True)
@@ -1158,9 +1171,24 @@ class Renderer(torch.nn.Module):
                 verts, faces, self.mesh_stats["edge_ids"] = mesh.keep_components(verts, faces, stats, stats["kept"], self.mesh_stats["edge_ids"])
                 self.mesh_stats["components"] = stats
             nrm = None
-            if extra:
+            if simplify is not None:
+                if refine:
+                    verts, _ = self._refine_mesh(network, verts, faces, res, lo, step, float(level), refine, None, shapeCodes, expType,
+                                                 expCodes, netchunk)
+                cell = (np.float32(int(simplify)) * np.asarray(step, dtype=np.float32)).astype(np.float32)
+                verts, faces, self.mesh_stats["simplify"] = mesh.simplify(verts.contiguous(), faces.contiguous(), cell, origin=lo,
+                                                                          placement=placement)
+                self.mesh_stats.pop("edge_ids", None)
+                if normals is not None:
+                    verts, nrm = self._refine_mesh(network, verts, faces, res, lo, step, float(level), 0, normals, shapeCodes, expType,
+                                                   expCodes, netchunk)
+            elif extra:
                 verts, nrm = self._refine_mesh(network, verts, faces, res, lo, step, float(level), refine, normals, shapeCodes, expType,
                                                expCodes, netchunk)
+            if normals == "density" and isinstance(self.mesh_stats, dict):
+                self.mesh_stats["normal_evaluations"] = 6 * int(verts.shape[0])
+            if colors and isinstance(self.mesh_stats, dict):
+                self.mesh_stats["color_evaluations"] = int(verts.shape[0])
             tail = () if nrm is None else (nrm,)
             if not colors:
                 return (verts, faces) + tail

@@ -24,6 +24,12 @@ placement of a grid 2^K times finer along each edge; faces unchanged), and ``--n
 GPU and only the one with the most faces, or every one with at least N faces, is kept; the tool prints the largest components (faces,
 area, signed volume, box) and what was removed.  With ``--time`` it also prints the labelling's passes and the time of each stage next to
 the extraction's.  ON SEEDED WEIGHTS THE COMPONENTS SAY NOTHING ABOUT THE FLOATERS OF A TRAINED FACE: a seeded network's density is noise.
+
+``--simplify M`` simplifies the mesh by vertex clustering on cells of M grid steps with one quadric-error representative per cluster
+(``mesh.simplify``; ``--placement mean`` is plain clustering, the baseline), after ``--components`` and ``--refine`` and before
+``--normals`` and ``--colors``; the tool prints the counts before and after and how the representatives were placed.  The result is
+closed where the input is, not necessarily manifold.  What the method does to a trained face has not been measured: seeded weights say
+nothing about it.
 """
 import argparse
 import itertools
@@ -91,6 +97,26 @@ def components_report(st, top=8):
           f"{float(area[gone].sum()):.6g}, volume {float(volume[gone].sum()):.6g}")
 
 
+def simplify_arg(text):
+    try:
+        m = int(text)
+    except ValueError:
+        m = 0
+    if m < 2:
+        raise argparse.ArgumentTypeError(f"{text!r}: want an integer >= 2 (grid steps per cell)")
+    return m
+
+
+def simplify_report(st):
+    """Counts before and after and the placement routes (render.mesh_stats["simplify"])."""
+    print(f"simplified: {st['verts_in']} vertices / {st['faces_in']} faces -> {st['verts_out']} / {st['faces_out']} "
+          f"({st['faces_in'] / max(st['faces_out'], 1):.1f}x fewer faces); {st['n_clusters']} clusters, {st['faces_degenerate']} faces collapsed, "
+          f"{st['faces_cancelled']} cancelled as fins")
+    print(f"  representatives: {st['placed_quadric']} at the quadric minimiser, {st['placed_mean']} at the cluster mean "
+          f"({st['mean_requested']} of them requested), {st['placed_first']} at the first vertex; {st['edges_multiple']} directed edges are used "
+          f"by more than one face (non-manifold there)")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     src = ap.add_mutually_exclusive_group(required=True)
@@ -114,7 +140,13 @@ def main(argv=None):
                     "field's (central differences at half a grid step) or the area-weighted face normals")
     ap.add_argument("--components", type=components_arg, default=None, metavar="largest|N", help="remove floaters: keep the connected "
                     "component with the most faces, or every component with at least N faces (before --refine / --normals / --colors)")
+    ap.add_argument("--simplify", type=simplify_arg, default=None, metavar="M", help="simplify by vertex clustering on cells of M grid steps "
+                    "(after --components / --refine, before --normals / --colors)")
+    ap.add_argument("--placement", choices=("quadric", "mean"), default="quadric", help="with --simplify: the quadric-error representative "
+                    "or the cluster mean (plain clustering)")
     a = ap.parse_args(argv)
+    if a.compare_dense and a.simplify is not None:
+        ap.error("--compare-dense compares the unsimplified meshes: drop --simplify")
     if a.compare_dense and a.components is not None:
         ap.error("--compare-dense compares the unfiltered meshes: drop --components")
     if a.compare_dense and a.brick is None:
@@ -127,7 +159,7 @@ def main(argv=None):
     res = tuple(a.resolution)
     kw = dict(bounds=bounds, resolution=res, shapeCodes=bm, expType=20, expCodes=exp, netchunk=a.netchunk)
     out = render.extract_mesh(net, level=a.level, uvCodes=uv if a.colors else None, colors=a.colors, brick=a.brick, refine=a.refine,
-                              normals=a.normals, components=a.components, **kw)
+                              normals=a.normals, components=a.components, simplify=a.simplify, placement=a.placement, **kw)
     verts, faces = out[0], out[1]
     mesh.write_ply(a.out, verts, faces, out[2] if a.colors else None, normals=out[-1] if a.normals else None)
     print(f"wrote {a.out}: V = {verts.shape[0]}, F = {faces.shape[0]}")
@@ -137,6 +169,10 @@ def main(argv=None):
         components_report(render.mesh_stats["components"])
     if a.refine:
         print(f"refined by {a.refine} bisection steps: {render.mesh_stats['refine']['evaluations']} density evaluations at the vertices' edges")
+    if a.simplify is not None:
+        if a.synthetic:
+            print("seeded synthetic weights: the simplification below says NOTHING about what the method does to a trained face")
+        simplify_report(render.mesh_stats["simplify"])
     if a.normals == "density":
         print(f"density normals: {render.mesh_stats['zero_normals']} of {verts.shape[0]} vertices have a vanishing gradient")
     if a.brick is not None:
@@ -190,6 +226,13 @@ def main(argv=None):
         print(f"components: {st['n_components']} in {st['passes']} passes, {t_cc * 1e3:9.3f} ms = {100 * t_cc / t_iso:.1f} % of the extraction "
               f"(phases, each ended by a synchronisation, ms: {phases})")
         print(f"compaction to {kept[0].shape[0]} vertices / {kept[1].shape[0]} faces with one companion: {t_keep * 1e3:9.3f} ms")
+    if a.simplify is not None:
+        cell = (a.simplify * step).astype(step.dtype)                  # extract_mesh's cell: M grid steps, in float32
+        t_simp, _ = timed(lambda: mesh.simplify(v2, f2, cell, origin=lo, placement=a.placement))
+        _, (_, _, st_t) = timed(lambda: mesh.simplify(v2, f2, cell, origin=lo, placement=a.placement, timing=True), reps=1)
+        phases = ", ".join(f"{k} {v * 1e3:.3f}" for k, v in st_t["times"].items())
+        print(f"simplification of the unfiltered mesh at {a.simplify} steps: {t_simp * 1e3:9.3f} ms = {100 * t_simp / t_iso:.1f} % of the extraction "
+              f"(phases, each ended by a synchronisation, ms: {phases})")
 
 
 def renumbered(verts, faces, edge_ids):

@@ -9,7 +9,10 @@ Writes ``level_<level>_mesh.png`` (head-light shade) and ``level_<level>_mesh_de
 ``--out``; prints one JSON line at the end.  ``--refine K`` extracts every level a second time with its vertices moved onto the level by
 K bisection steps along their lattice edges (``extract_mesh(refine=K)``) and prints the agreement without and with: the difference is
 what the linear vertex placement contributed to the first number.  ``--components largest|N`` is passed to ``extract_mesh``: floaters
-are removed before the mesh is rasterised, so a level's agreement can be read with and without them.
+are removed before the mesh is rasterised, so a level's agreement can be read with and without them.  ``--simplify M`` extracts every
+level once more with ``extract_mesh(simplify=M)`` (vertex clustering on cells of M grid steps, quadric-error representatives), rasterises
+it from the same pose and prints its agreement with the volume next to the unsimplified mesh's, and the agreement of the simplified mesh
+with the unsimplified one (the unsimplified mesh's mask standing in as ``acc`` with ``acc_min`` 0.5): what the simplification cost in depth.
 
 Networks come from a checkpoint (``--ckpt``) or seeded synthetic weights (``--synthetic DC WC DF WF``), codes from ``--fit`` or
 ``synth.codes`` — the options of tools/render_geometry.py.  ON SEEDED WEIGHTS THE AGREEMENT NUMBERS MEAN NOTHING ABOUT A TRAINED FACE:
@@ -30,7 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mofanerf_amd import mesh, synth  # noqa: E402
 from mofanerf_amd.io import PngSink  # noqa: E402
 from mofanerf_amd.rays import pose_spherical  # noqa: E402
-from extract_mesh import components_arg  # noqa: E402
+from extract_mesh import components_arg, simplify_arg  # noqa: E402
 from render_culled import load  # noqa: E402
 
 
@@ -65,6 +68,8 @@ def main(argv=None):
                     "bisection steps along their edges (extract_mesh(refine=K)); the agreement is printed without and with")
     ap.add_argument("--components", type=components_arg, default=None, metavar="largest|N", help="remove floaters before rasterising: "
                     "extract_mesh(components=...) keeps the component with the most faces, or every one with at least N faces")
+    ap.add_argument("--simplify", type=simplify_arg, default=None, metavar="M", help="also extract every level simplified on cells of M grid "
+                    "steps (extract_mesh(simplify=M)); its agreement with the volume and with the unsimplified mesh is printed")
     ap.add_argument("--size", type=int, default=512, help="frame height = width")
     ap.add_argument("--samples", type=int, nargs=2, default=[64, 128], metavar=("N_SAMPLES", "N_IMPORTANCE"))
     ap.add_argument("--near", type=float, default=8.0)
@@ -137,9 +142,33 @@ def main(argv=None):
                 stem = os.path.join(a.out, f"level_{level:g}" + (f"_refine{k}" if k else ""))
                 sink.submit(stem + "_mesh.png", rgb)
                 sink.submit(stem + "_mesh_depth.png", (((depth - a.near) / span) * mask)[..., None].expand(H, H, 3))
+                if a.simplify is None:
+                    continue
+                # the same mesh simplified, from the same pose: against the volume, and against the unsimplified mesh
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                sv, sf = render.extract_mesh(net, bounds=bounds, resolution=tuple(a.resolution), level=level, shapeCodes=bm, expType=20,
+                                             expCodes=exp, netchunk=a.netchunk, brick=a.brick, refine=k, components=a.components,
+                                             simplify=a.simplify)[:2]
+                torch.cuda.synchronize()
+                t_simp = (time.perf_counter() - t0) * 1e3
+                ss = {key: val for key, val in render.mesh_stats["simplify"].items() if key != "cluster_of"}
+                t_smesh, _, (srgb, sdepth, smask, _) = median_ms(lambda: render.render_mesh(H, H, K, pose, sv, sf, znear=a.znear), a.warmup, a.frames)
+                s_vol = mesh.depth_agreement(sdepth, smask, depth_vol, acc, a.acc_min)
+                s_full = mesh.depth_agreement(sdepth, smask, depth, mask.to(torch.float32), 0.5)
+                row["simplified"] = {"simplify": a.simplify, "extract_ms": round(t_simp, 2), "render_mesh_ms": t_smesh, **ss,
+                                     "against_volume": s_vol, "against_unsimplified": s_full}
+                print(f"  simplify={a.simplify}: V = {ss['verts_out']}, F = {ss['faces_out']} ({ss['faces_in'] / max(ss['faces_out'], 1):.1f}x fewer faces; "
+                      f"placed {ss['placed_quadric']} quadric / {ss['placed_mean']} mean / {ss['placed_first']} first vertex, {ss['edges_multiple']} "
+                      f"directed edges used twice); extract + simplify {t_simp:.1f} ms, render_mesh {t_smesh:.3f} ms", flush=True)
+                print(f"    against the volume:      IoU {s_vol['iou']:.4f} (unsimplified {agree['iou']:.4f}), |depth difference| median "
+                      f"{s_vol['median_abs']:.5f} (unsimplified {agree['median_abs']:.5f}), 95 % {s_vol['p95_abs']:.5f} (unsimplified {agree['p95_abs']:.5f})")
+                print(f"    against the unsimplified mesh: IoU {s_full['iou']:.4f}, |depth difference| median {s_full['median_abs']:.5f}, "
+                      f"95 % {s_full['p95_abs']:.5f}", flush=True)
+                sink.submit(stem + f"_simplify{a.simplify}_mesh.png", srgb)
     print(json.dumps({"size": H, "samples": a.samples, "angle": a.angle, "radius": a.radius, "near": a.near, "far": a.far, "acc_min": a.acc_min,
                       "median_threshold": a.median_threshold, "resolution": a.resolution, "brick": a.brick, "refine": a.refine, "components": a.components,
-                      "wave_min_pixels": mesh.WAVE_MIN_PIXELS, "synthetic_weights": bool(a.synthetic),
+                      "simplify": a.simplify, "wave_min_pixels": mesh.WAVE_MIN_PIXELS, "synthetic_weights": bool(a.synthetic),
                       "agreement_says_nothing_about_a_trained_face": bool(a.synthetic), "render_geometry_ms": t_vol,
                       "render_geometry_ms_all": all_vol, "levels": rows, "out": a.out}))
 
