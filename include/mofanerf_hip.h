@@ -384,6 +384,79 @@ int mofa_simp_place(const double* quadrics, const double* vsum, const int64_t* c
 int mofa_simp_faces(const int32_t* faces, int64_t F, int64_t V, const int32_t* cluster, int64_t C, int32_t* out, uint8_t* degenerate,
                     int64_t* counts, void* stream);
 
+/* Mesh surface distance: the exact closest point on a triangle mesh (verts [V,3] float, faces [F,3] int32) for N query points through a
+ * uniform grid of face lists, and a deterministic quadrature of a surface (mesh.py drives the passes: mesh.closest_points,
+ * mesh.sample_faces, mesh.surface_distance; 1 <= N, V, F, P, S <= 2^31 - 1).  No float or double atomics: the same input gives the same
+ * bytes every time; the only atomics are the integer counters counts[MOFA_DIST_COUNTS] (int64, DEVICE, zeroed by the caller).  Every kernel
+ * checks the indices it dereferences: a bad one is skipped.  No kernel waits on another thread.  All arithmetic is fp64 on the fp32
+ * coordinates widened, every operation rounded separately; dot(x, y) = (x0 y0 + x1 y1) + x2 y2.
+ *   the triangle       closest point q of (a, b, c) to p, in Ericson's region order:
+ *                        ab = b - a, ac = c - a, ap = p - a;  d1 = dot(ab, ap), d2 = dot(ac, ap);  d1 <= 0 && d2 <= 0: q = a, bary (1, 0, 0)
+ *                        bp = p - b;  d3 = dot(ab, bp), d4 = dot(ac, bp);  d3 >= 0 && d4 <= d3: q = b, bary (0, 1, 0)
+ *                        vc = d1 d4 - d3 d2;  vc <= 0 && d1 >= 0 && d3 <= 0: v = d1 / (d1 - d3), q = a + v ab, bary (1 - v, v, 0)
+ *                        cp = p - c;  d5 = dot(ab, cp), d6 = dot(ac, cp);  d6 >= 0 && d5 <= d6: q = c, bary (0, 0, 1)
+ *                        vb = d5 d2 - d1 d6;  vb <= 0 && d2 >= 0 && d6 <= 0: w = d2 / (d2 - d6), q = a + w ac, bary (1 - w, 0, w)
+ *                        va = d3 d6 - d5 d4, e = d4 - d3, g = d5 - d6;  va <= 0 && e >= 0 && g >= 0: w = e / (e + g), q = b + w (c - b),
+ *                          bary (0, 1 - w, w)
+ *                        s = (va + vb) + vc;  s not finite or s <= 0: the face is skipped for this point (counts[MOFA_DIST_SKIPPED]);
+ *                        v = vb / s, w = vc / s, q = (a + v ab) + w ac, bary ((1 - v) - w, v, w)
+ *                      then per axis q = q < lo ? lo : q, q = q > hi ? hi : q with lo / hi the smallest / largest of the three vertices
+ *                      (the closest point lies in the triangle's box: this removes rounding only), and d2 = ((px - qx)^2 + (py - qy)^2) +
+ *                      (pz - qz)^2.  Across faces the smaller d2 wins, among equal d2 the lower face index, a NaN d2 never: the answer is a
+ *                      function of the mesh and the point alone.
+ *   the grid           n[3] cells (1 .. MOFA_DIST_MAX_GRID per axis, fewer than 2^31 - 1 in all) from origin[3] with cell[3] > 0 (HOST arrays
+ *                      of doubles).  The cell of a coordinate x: t = floor((x - origin) / cell), index = t >= 0 ? (t < n ? (int) t : n - 1) : 0;
+ *                      cell id = (ix n[1] + iy) n[2] + iz.  A face whose normal ab x ac = (aby acz - abz acy, abz acx - abx acz, abx acy - aby acx)
+ *                      is exactly (0, 0, 0) is DEGENERATE: it enters no cell.  Every other face enters every cell of the index box of its
+ *                      three vertices.
+ *   mofa_dist_validate     counts[0] += the non-finite coordinates of verts
+ *   mofa_dist_bin_count    n_cells[f] (int64) = the cells face f enters; counts[MOFA_DIST_DEGENERATE] += the degenerate faces
+ *   mofa_dist_bin_emit     with offsets [F] (int64, DEVICE) = the exclusive sum of n_cells and P = its total: pair_cell / pair_face [P] (int32),
+ *                          face f's cells in ascending id from offsets[f].  The caller sorts the pairs stably by cell (each cell's faces then
+ *                          ascend) and forms cell_start [cells + 1] (int32): the pairs of cell c are cell_start[c] .. cell_start[c + 1] - 1.
+ *   mofa_dist_query        one thread per query; thread i takes query order[i] (int64 [N], DEVICE: a permutation that puts queries of one
+ *                          cell next to each other; NULL = the identity) and writes its slots of distance [N] (float: sqrt(d2) in fp64,
+ *                          rounded once), d2 [N] (double), face [N] (int32), closest [N,3] (float), bary [N,3] (float).  From the cell c of the
+ *                          point it visits the cells of Chebyshev ring r = 0, 1, 2, ... (clipped to the grid).  After ring r, for every axis
+ *                          and side on which the visited block has not reached the grid's edge (c - r > 0; c + r < n - 1):
+ *                            low:  ((p - (origin + (double)(c - r) cell)) - slack) (1 - 2^-40)
+ *                            high: (((origin + (double)(c + r + 1) cell) - p) - slack) (1 - 2^-40)
+ *                          and lb = the smallest of them: every face not yet seen has d2 > lb^2 when lb > 0 (slack[3] >= 0 covers the rounding
+ *                          of the cell arithmetic; DESIGN 3.17 derives how much it takes).  The walk ends when no such side is left, or when
+ *                          lb > 0 and (best d2 < lb lb, strictly: an equal d2 with a lower index may sit in the next ring; or lb > max_distance).
+ *                          max_distance > 0 (infinity: unbounded): a query whose sqrt(d2) is not <= max_distance, or that found no face,
+ *                          gets face -1, distance and d2 +infinity, closest and bary NaN.  A query with a non-finite coordinate gets face -1
+ *                          and NaN everywhere and is counted in counts[MOFA_DIST_NON_FINITE].  counts[MOFA_DIST_TESTS] += the point-triangle
+ *                          tests, counts[MOFA_DIST_MAX_RING] = max(the last ring of any query): both depend on the grid, no result bit does.
+ *                          pair_face may be NULL when P = 0.
+ *   mofa_dist_sample_count area[f] (double) = 0.5 sqrt((nx nx + ny ny) + nz nz) of the normal above and k[f] (int32) = ceil(sqrt(L) / spacing)
+ *                          clamped to 1 .. max_subdiv (<= MOFA_DIST_MAX_SUBDIV), L = the largest of dot(ab, ab), dot(ac, ac), dot(bc, bc) with
+ *                          bc = c - b; a degenerate face gets area 0 and k 0 (no samples)
+ *   mofa_dist_sample_emit  with offsets [F] (int64) = the exclusive sum of k^2, S its total and face_of [S] (int32) the face of every sample:
+ *                          sample offsets[f] + t is the centroid of sub-triangle t of the regular subdivision of face f into k^2 congruent
+ *                          triangles.  Row i = 0 .. k - 1 starts at t = 2 k i - i^2 and holds, for j = 0 .. k - 1 - i, the upright triangle
+ *                          (numerators nv = 3 i + 1, nw = 3 j + 1) and, for j < k - 1 - i, after it the inverted one (nv = 3 i + 2,
+ *                          nw = 3 j + 2); nu = 3 k - nv - nw.  points[s] = (float)(((nu a + nv b) + nw c) / (3 k)) per axis in fp64,
+ *                          weight[s] (double) = area[f] / (double)(k k).  A sample whose face_of / offsets do not fit gets NaN and weight 0. */
+enum { MOFA_DIST_DEGENERATE = 0, MOFA_DIST_NON_FINITE = 1, MOFA_DIST_TESTS = 2, MOFA_DIST_MAX_RING = 3, MOFA_DIST_SKIPPED = 4,
+       MOFA_DIST_COUNTS = 5 };
+#define MOFA_DIST_MAX_GRID 1024
+#define MOFA_DIST_MAX_SUBDIV 1024
+int mofa_dist_validate(const float* verts, int64_t V, int64_t* counts, void* stream);
+int mofa_dist_bin_count(const float* verts, const int32_t* faces, int64_t F, int64_t V, const double origin[3], const double cell[3],
+                        const double slack[3], const int32_t n[3], int64_t* n_cells, int64_t* counts, void* stream);
+int mofa_dist_bin_emit(const float* verts, const int32_t* faces, int64_t F, int64_t V, const double origin[3], const double cell[3],
+                       const double slack[3], const int32_t n[3], const int64_t* offsets, int64_t P, int32_t* pair_cell, int32_t* pair_face,
+                       void* stream);
+int mofa_dist_query(const float* points, int64_t N, const int64_t* order, const float* verts, int64_t V, const int32_t* faces, int64_t F,
+                    const double origin[3], const double cell[3], const double slack[3], const int32_t n[3], const int32_t* cell_start,
+                    const int32_t* pair_face, int64_t P, double max_distance, float* distance, double* d2, int32_t* face, float* closest,
+                    float* bary, int64_t* counts, void* stream);
+int mofa_dist_sample_count(const float* verts, const int32_t* faces, int64_t F, int64_t V, double spacing, int32_t max_subdiv, double* area,
+                           int32_t* k, void* stream);
+int mofa_dist_sample_emit(const float* verts, const int32_t* faces, int64_t F, int64_t V, const double* area, const int32_t* k,
+                          const int64_t* offsets, const int32_t* face_of, int64_t S, float* points, double* weight, void* stream);
+
 /* ---- occupancy-culled rendering: skip the network where an occupancy grid says the space is empty ---------------------------------
  * The grid lives on the lattice of mofa_grid_points (nx x ny x nz samples at lo + (i,j,k) step): (nx-1)(ny-1)(nz-1) cells, one byte
  * each (0 / 1), cell index (i (ny-1) + j) (nz-1) + k.  The lattice needs 2 <= n < 2^24 per axis and fewer than 2^31 cells.

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("MOFA_LIB") or os.path.join(_HERE, "libmofanerf_hip.so
 _f = C.POINTER(C.c_float)
 _fp = C.c_void_p      # device pointers travel as integers
 _i32, _i64, _sz = C.c_int32, C.c_int64, C.c_size_t
+_d3 = C.POINTER(C.c_double)
 
 
 ABI_VERSION = 5
@@ -92,6 +93,13 @@ SIGNATURES = {
     "mofa_simp_place": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i64, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_double, _i32, _fp, _fp,
                                   _fp]),
     "mofa_simp_faces": (C.c_int, [_fp, _i64, _i64, _fp, _i64, _fp, _fp, _fp, _fp]),
+    "mofa_dist_validate": (C.c_int, [_fp, _i64, _fp, _fp]),
+    "mofa_dist_bin_count": (C.c_int, [_fp, _fp, _i64, _i64, _d3, _d3, _d3, C.POINTER(_i32), _fp, _fp, _fp]),
+    "mofa_dist_bin_emit": (C.c_int, [_fp, _fp, _i64, _i64, _d3, _d3, _d3, C.POINTER(_i32), _fp, _i64, _fp, _fp, _fp]),
+    "mofa_dist_query": (C.c_int, [_fp, _i64, _fp, _fp, _i64, _fp, _i64, _d3, _d3, _d3, C.POINTER(_i32), _fp, _fp, _i64, C.c_double, _fp, _fp,
+                                  _fp, _fp, _fp, _fp, _fp]),
+    "mofa_dist_sample_count": (C.c_int, [_fp, _fp, _i64, _i64, C.c_double, _i32, _fp, _fp, _fp]),
+    "mofa_dist_sample_emit": (C.c_int, [_fp, _fp, _i64, _i64, _fp, _fp, _fp, _fp, _i64, _fp, _fp, _fp]),
     "mofa_occ_workspace_bytes": (_sz, [_i64]),
     "mofa_occ_cells": (C.c_int, [_fp, _i64, _i64, _i64, C.c_float, _i32, _fp, _fp]),
     "mofa_occ_dilate": (C.c_int, [_fp, _i64, _i64, _i64, _i32, _fp, _fp, _fp]),

@@ -5,6 +5,8 @@ density normals (``refine_vertices``, ``density_normals``, ``mofa_edge_*`` / ``m
 ``mofa_raster_*``) whose depth is comparable with ``Renderer.render_geometry``'s, and ``depth_agreement`` between the two.
 ``components`` labels a mesh's connected components (``mofa_cc_*``) with their sizes, areas, signed volumes and boxes;
 ``select_components`` / ``keep_components`` drop the floaters among them.
+``simplify`` clusters a mesh's vertices (``mofa_simp_*``); ``closest_points`` finds the exact closest point of a mesh to every query,
+``sample_faces`` samples a surface deterministically and ``surface_distance`` measures one mesh against another (``mofa_dist_*``).
 
 ``Renderer.query_density`` and ``Renderer.extract_mesh`` are the user-facing entry points; this module holds the pieces they share.
 The mesh is watertight and consistently oriented (normals toward lower density); vertices and faces come out in a fixed order with
@@ -733,6 +735,282 @@ def simplify(verts: torch.Tensor, faces: torch.Tensor, cell, origin=None, regula
     return out_v, out_f, stats
 
 
+# ---- surface distance ------------------------------------------------------------------------------------------------------------------
+# closest_points' default grid: cells of DIST_GRID_FACTOR estimated face edges (edge^2 = the box's surface area / F), at most
+# DIST_GRID_AUTO_CAP per axis; DIST_GRID_CAP is the most a caller may force.  The resolution changes no bit of the result;
+# profiles/mesh_distance.md holds the sweep the numbers come from.
+DIST_GRID_CAP = 256
+DIST_GRID_AUTO_CAP = 128
+DIST_GRID_FACTOR = 2.0
+DIST_MAX_SUBDIV = 1024                                                                                     # MOFA_DIST_MAX_SUBDIV
+_DIST_COUNTS = ("degenerate_faces", "non_finite_queries", "candidate_tests", "max_ring", "skipped_tests")       # MOFA_DIST_* of the header
+
+
+def _d3(v) -> C.Array:
+    return (C.c_double * 3)(*[float(x) for x in v])
+
+
+def dist_grid(lo, hi, n):
+    """(origin [3], cell [3], slack [3]) in float64 of closest_points' grid of ``n`` cells over the box ``lo .. hi``: ``cell = (hi - lo) / n``
+    (1 on an axis of no extent: everything falls into its cell 0) and ``slack = 2^-40 (|origin| + n cell)``, what the query's termination
+    bound gives away to the rounding of the cell arithmetic."""
+    origin = np.asarray(lo, dtype=np.float64).reshape(3)
+    extent = np.asarray(hi, dtype=np.float64).reshape(3) - origin
+    nn = np.asarray(n, dtype=np.float64).reshape(3)
+    cell = np.where(extent > 0, extent / nn, 1.0)
+    return origin, cell, 2.0 ** -40 * (np.abs(origin) + nn * cell)
+
+
+def default_dist_grid(lo, hi, F: int):
+    """The resolution closest_points picks for ``F`` faces in the box ``lo .. hi``: ``ceil(extent / h)`` cells per axis, ``h`` =
+    DIST_GRID_FACTOR sqrt(the box's surface area / F), clamped to 1 .. DIST_GRID_AUTO_CAP."""
+    e = np.asarray(hi, dtype=np.float64).reshape(3) - np.asarray(lo, dtype=np.float64).reshape(3)
+    area = 2.0 * (e[0] * e[1] + e[1] * e[2] + e[0] * e[2])
+    if not (F > 0 and area > 0 and np.isfinite(area)):
+        return (1, 1, 1)
+    h = DIST_GRID_FACTOR * np.sqrt(area / F)
+    return tuple(int(v) for v in np.clip(np.ceil(e / h), 1, DIST_GRID_AUTO_CAP))
+
+
+def _query_points(who, points, dev):
+    lib.ptr(points)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise lib.MofaError(f"{who}: want points [N,3], got {tuple(points.shape)}")
+    if points.device != dev:
+        raise lib.MofaError(f"{who}: points on {points.device}, the mesh on {dev}")
+    if points.shape[0] > INT32_MAX:
+        raise lib.MofaError(f"{who}: {points.shape[0]} points exceed the int32 indices (2^31 - 1)")
+    return int(points.shape[0])
+
+
+def _max_distance(who, max_distance) -> float:
+    if max_distance is None:
+        return float("inf")
+    m = float(max_distance)
+    if not m > 0:
+        raise lib.MofaError(f"{who}: max_distance = {max_distance} (want > 0, or None for unbounded)")
+    return m
+
+
+def closest_points(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, grid=None, max_distance=None) -> dict:
+    """The exact closest point of the triangle mesh ``(verts [V,3] float32, faces [F,3] int32)`` to every one of ``points [N,3] float32``, on
+    the GPU (``mofa_dist_*``).  Returns a dict: ``distance [N] float32``, ``d2 [N] float64`` (squared), ``face [N] int32`` (the winning
+    face), ``closest [N,3] float32``, ``bary [N,3] float32`` (barycentrics of the closest point on that face), ``counts`` (a dict:
+    ``degenerate_faces``, ``non_finite_queries``, ``candidate_tests``, ``max_ring``, ``skipped_tests``) and ``grid`` (the resolution used).
+
+    Point and triangle are widened to fp64 and go through Ericson's region tests in a fixed order of operations
+    (include/mofanerf_hip.h); the smaller squared distance wins, among equal ones the lower face index.  The answer is therefore a function
+    of the mesh and the point alone: the faces are binned into a uniform grid over the mesh's box and every query walks Chebyshev rings
+    of cells around its own until a conservative bound shows that no unseen face can win or tie, and the resolution of that grid —
+    ``grid``: ``None`` (``default_dist_grid``), an int or a triple, 1 .. DIST_GRID_CAP per axis — changes the time but no bit of the
+    result; ``grid=1`` is brute force through the same kernel.  No float atomics: the same bytes every time.
+
+    A face whose fp64 normal is exactly zero is degenerate: skipped and counted.  ``max_distance`` (> 0) bounds the search: a query whose
+    closest face is farther gets face -1, distance ``inf`` (``closest`` / ``bary`` NaN); within the bound the bits are those of the
+    unbounded call.  A query with a non-finite coordinate gets face -1 and NaN and is counted, not refused.  ``N == 0`` returns empty tensors
+    without a launch; ``F == 0``, or only degenerate faces, gives face -1 and distance ``inf`` everywhere.
+
+    Raises ``MofaError`` for CPU tensors, wrong dtypes or shapes, a face index outside the mesh (after ``mofa_cc_validate``, before any
+    other kernel), a non-finite target vertex, ``max_distance`` not > 0 and a grid outside 1 .. DIST_GRID_CAP.  No signed distance: a sign
+    taken from the closest face's normal is wrong at edges and vertices."""
+    who = "closest_points"
+    V, F, dev = _mesh_tensors(who, verts, faces)
+    N = _query_points(who, points, dev)
+    maxd = _max_distance(who, max_distance)
+    if grid is not None:
+        g = np.asarray(grid).reshape(-1)
+        if g.size not in (1, 3) or g.dtype.kind not in "iu" or (g < 1).any() or (g > DIST_GRID_CAP).any():
+            raise lib.MofaError(f"{who}: grid = {grid!r} (want None, an integer or three, 1 .. {DIST_GRID_CAP} per axis)")
+        grid = tuple(int(v) for v in (np.repeat(g, 3) if g.size == 1 else g))
+    out = {"distance": torch.full((N,), float("inf"), dtype=torch.float32, device=dev),
+           "d2": torch.full((N,), float("inf"), dtype=torch.float64, device=dev), "face": torch.full((N,), -1, dtype=torch.int32, device=dev),
+           "closest": torch.full((N, 3), float("nan"), dtype=torch.float32, device=dev),
+           "bary": torch.full((N, 3), float("nan"), dtype=torch.float32, device=dev), "counts": dict.fromkeys(_DIST_COUNTS, 0),
+           "grid": grid if grid is not None else (1, 1, 1)}
+    if N == 0:
+        return out
+    if V == 0 or F == 0:
+        bad = ~torch.isfinite(points).all(1)
+        out["distance"][bad], out["d2"][bad] = float("nan"), float("nan")
+        out["counts"]["non_finite_queries"] = int(bad.sum())
+        return out
+    L = lib.load()
+    i64 = dict(dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        stream = lib.stream()
+        bad = torch.zeros(1, **i64)
+        lib.check(L.mofa_cc_validate(faces.data_ptr(), F, V, bad.data_ptr(), stream), "mofa_cc_validate")
+        n_bad = int(bad.cpu()[0])
+        if n_bad:
+            raise lib.MofaError(f"{who}: {n_bad} of the {3 * F} face indices lie outside [0, {V})")
+        bad.zero_()
+        lib.check(L.mofa_dist_validate(lib.ptr(verts), V, bad.data_ptr(), stream), "mofa_dist_validate")
+        n_bad = int(bad.cpu()[0])
+        if n_bad:
+            raise lib.MofaError(f"{who}: {n_bad} of the {3 * V} coordinates of the target mesh are not finite")
+        box = torch.stack([verts.amin(0), verts.amax(0)]).cpu().numpy()
+        if grid is None:
+            grid = default_dist_grid(box[0], box[1], F)
+        out["grid"] = grid
+        origin, cell, slack = dist_grid(box[0], box[1], grid)
+        o3, c3, s3, n3 = _d3(origin), _d3(cell), _d3(slack), (C.c_int32 * 3)(*grid)
+        n_cells = grid[0] * grid[1] * grid[2]
+        counts = torch.zeros(len(_DIST_COUNTS), **i64)
+        per_face = torch.empty(F, **i64)
+        lib.check(L.mofa_dist_bin_count(lib.ptr(verts), faces.data_ptr(), F, V, o3, c3, s3, n3, per_face.data_ptr(), counts.data_ptr(), stream),
+                  "mofa_dist_bin_count")
+        ends = torch.cumsum(per_face, 0)
+        P = int(ends[-1].cpu())
+        if P > INT32_MAX:
+            raise lib.MofaError(f"{who}: the {F} faces enter {P} cells of the {grid} grid, more than 2^31 - 1: take a coarser grid")
+        start = torch.zeros(n_cells + 1, dtype=torch.int32, device=dev)
+        pair_face = torch.empty(P, dtype=torch.int32, device=dev)
+        if P:
+            offsets = (ends - per_face).contiguous()
+            pair_cell = torch.empty(P, dtype=torch.int32, device=dev)
+            lib.check(L.mofa_dist_bin_emit(lib.ptr(verts), faces.data_ptr(), F, V, o3, c3, s3, n3, offsets.data_ptr(), P, pair_cell.data_ptr(),
+                                           pair_face.data_ptr(), stream), "mofa_dist_bin_emit")
+            if n_cells > 1:
+                by_cell = torch.sort(pair_cell, stable=True).indices
+                pair_face = pair_face[by_cell].contiguous()
+                del by_cell
+            start[1:] = torch.cumsum(torch.bincount(pair_cell.long(), minlength=n_cells), 0).to(torch.int32)
+            del pair_cell, offsets
+        order = None
+        if n_cells > 1:                          # queries of one cell next to each other: a wavefront's lanes walk the same neighbourhood
+            t = torch.nan_to_num((points.double() - torch.from_numpy(origin).to(dev)) / torch.from_numpy(cell).to(dev), nan=0.0, posinf=0.0,
+                                 neginf=0.0).floor_()
+            hi = torch.tensor([g - 1 for g in grid], dtype=torch.float64, device=dev)
+            c = torch.minimum(torch.clamp_(t, min=0.0), hi).long()
+            order = torch.argsort((c[:, 0] * grid[1] + c[:, 1]) * grid[2] + c[:, 2])
+            del t, c
+        lib.check(L.mofa_dist_query(lib.ptr(points), N, None if order is None else order.data_ptr(), lib.ptr(verts), V, faces.data_ptr(), F, o3, c3,
+                                    s3, n3, start.data_ptr(), pair_face.data_ptr() if P else None, P, maxd, lib.ptr(out["distance"]),
+                                    out["d2"].data_ptr(), out["face"].data_ptr(), lib.ptr(out["closest"]), lib.ptr(out["bary"]),
+                                    counts.data_ptr(), stream), "mofa_dist_query")
+        out["counts"] = dict(zip(_DIST_COUNTS, (int(v) for v in counts.cpu())))
+    return out
+
+
+def sample_faces(verts: torch.Tensor, faces: torch.Tensor, spacing: float, max_subdiv: int = 64):
+    """A deterministic quadrature of a mesh's surface (``mofa_dist_sample_*``; no random numbers): face f is cut into ``k_f^2`` congruent
+    triangles, ``k_f = clamp(ceil(longest edge / spacing), 1, max_subdiv)``, and sampled at their centroids, each with weight
+    ``area_f / k_f^2`` (fp64), so the weights of a face sum to its area.  Returns ``(points [S,3] float32, face_of [S] int32, weight [S]
+    float64)``: the faces in their order, each face's sub-triangles in the order the header states.  Degenerate faces (a zero fp64 normal)
+    emit nothing.  The same mesh gives the same bytes."""
+    who = "sample_faces"
+    V, F, dev = _mesh_tensors(who, verts, faces)
+    spacing = float(spacing)
+    if not (np.isfinite(spacing) and spacing > 0):
+        raise lib.MofaError(f"{who}: spacing = {spacing} (want finite and > 0)")
+    if isinstance(max_subdiv, (bool, np.bool_)) or max_subdiv != int(max_subdiv) or not 1 <= int(max_subdiv) <= DIST_MAX_SUBDIV:
+        raise lib.MofaError(f"{who}: max_subdiv = {max_subdiv!r} (want an integer 1 .. {DIST_MAX_SUBDIV})")
+    empty = (torch.zeros(0, 3, dtype=torch.float32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
+             torch.zeros(0, dtype=torch.float64, device=dev))
+    if V == 0 or F == 0:
+        return empty
+    L = lib.load()
+    with torch.cuda.device(dev):
+        stream = lib.stream()
+        bad = torch.zeros(1, dtype=torch.int64, device=dev)
+        lib.check(L.mofa_cc_validate(faces.data_ptr(), F, V, bad.data_ptr(), stream), "mofa_cc_validate")
+        n_bad = int(bad.cpu()[0])
+        if n_bad:
+            raise lib.MofaError(f"{who}: {n_bad} of the {3 * F} face indices lie outside [0, {V})")
+        area = torch.empty(F, dtype=torch.float64, device=dev)
+        k = torch.empty(F, dtype=torch.int32, device=dev)
+        lib.check(L.mofa_dist_sample_count(lib.ptr(verts), faces.data_ptr(), F, V, spacing, int(max_subdiv), area.data_ptr(), k.data_ptr(), stream),
+                  "mofa_dist_sample_count")
+        k2 = k.long() ** 2
+        ends = torch.cumsum(k2, 0)
+        S = int(ends[-1].cpu())
+        if S > INT32_MAX:
+            raise lib.MofaError(f"{who}: spacing {spacing} asks for {S} samples, more than 2^31 - 1")
+        if S == 0:
+            return empty
+        offsets = (ends - k2).contiguous()
+        face_of = torch.repeat_interleave(torch.arange(F, dtype=torch.int32, device=dev), k2, output_size=S)
+        pts = torch.empty(S, 3, dtype=torch.float32, device=dev)
+        weight = torch.empty(S, dtype=torch.float64, device=dev)
+        lib.check(L.mofa_dist_sample_emit(lib.ptr(verts), faces.data_ptr(), F, V, area.data_ptr(), k.data_ptr(), offsets.data_ptr(),
+                                          face_of.data_ptr(), S, lib.ptr(pts), weight.data_ptr(), stream), "mofa_dist_sample_emit")
+    return pts, face_of, weight
+
+
+def _distance_stats(d: torch.Tensor, weight: torch.Tensor, found: torch.Tensor) -> dict:
+    """mean / rms / p50 / p95 over the samples with a weight, max over all of them, of the distances ``d`` (float64) that were found."""
+    nan = float("nan")
+    out = {"mean": nan, "rms": nan, "max": nan, "p50": nan, "p95": nan}
+    d, weight = d[found], weight[found]
+    if d.numel():
+        out["max"] = float(d.max())
+    keep = weight > 0
+    d, weight = d[keep], weight[keep]
+    total = weight.sum()
+    if d.numel() and float(total) > 0:
+        out["mean"] = float((weight * d).sum() / total)
+        out["rms"] = float(torch.sqrt((weight * (d * d)).sum() / total))
+        ds, by = torch.sort(d, stable=True)
+        cum = torch.cumsum(weight[by], 0)
+        for name, q in (("p50", 0.5), ("p95", 0.95)):
+            i = torch.searchsorted(cum, (q * total).reshape(1)).clamp_(max=ds.numel() - 1)
+            out[name] = float(ds[i])
+    return out
+
+
+def surface_distance(verts_a: torch.Tensor, faces_a: torch.Tensor, verts_b: torch.Tensor, faces_b: torch.Tensor, spacing: float,
+                     max_distance=None, vertices: bool = True, timing: bool = False, samples: bool = False, max_subdiv: int = 64) -> dict:
+    """Surface distance between two triangle meshes on the GPU, both ways.  For ``a_to_b``: the quadrature samples of mesh a
+    (:func:`sample_faces` with ``spacing`` and ``max_subdiv``) plus, with ``vertices=True``, the vertices a's faces reference with weight 0
+    — they count in ``max`` and not in the means: a Hausdorff distance is often attained at a vertex, which no centroid reaches —
+    are sent through :func:`closest_points` against mesh b.  Each direction gives ``mean`` and ``rms`` (area-weighted, fp64), ``max``,
+    the weighted ``p50`` / ``p95``, ``n_samples`` and ``n_beyond`` (queries farther than ``max_distance``: left out of the statistics and
+    counted) and ``counts`` (closest_points' counters); ``samples=True`` adds ``points``, ``weight``, ``distance`` (fp64, sqrt of ``d2``)
+    and ``face``.  The dict also holds ``hausdorff`` (the larger of the two maxima) and ``chamfer`` (the sum of the two means), and with
+    ``timing=True`` ``times``: seconds of ``sample``, ``query`` and ``stats`` per direction, each ended by a device synchronisation.
+    A direction without samples, or with every sample beyond the bound, has NaN statistics.  The distances are unsigned."""
+    who = "surface_distance"
+    _mesh_tensors(who, verts_a, faces_a)
+    _mesh_tensors(who, verts_b, faces_b)
+    _max_distance(who, max_distance)
+    out, times = {}, {}
+
+    def lap(name, since):
+        if timing:
+            torch.cuda.synchronize(verts_a.device)
+            times[name] = time.perf_counter() - since
+        return time.perf_counter()
+
+    for name, (va, fa, vb, fb) in (("a_to_b", (verts_a, faces_a, verts_b, faces_b)), ("b_to_a", (verts_b, faces_b, verts_a, faces_a))):
+        clock = lap("start", 0.0)
+        pts, _, weight = sample_faces(va, fa, spacing, max_subdiv)
+        if vertices and fa.numel():
+            ref = torch.zeros(va.shape[0], dtype=torch.bool, device=va.device)
+            ref[fa.reshape(-1).long()] = True
+            pts = torch.cat([pts, va[ref]]).contiguous()
+            weight = torch.cat([weight, torch.zeros(pts.shape[0] - weight.shape[0], dtype=torch.float64, device=va.device)])
+        clock = lap(name + ".sample", clock)
+        res = closest_points(pts, vb, fb, max_distance=max_distance)
+        clock = lap(name + ".query", clock)
+        found = res["face"] >= 0
+        d = torch.sqrt(res["d2"])
+        st = _distance_stats(d, weight, found)
+        st["n_samples"] = int(pts.shape[0])
+        st["n_beyond"] = int((~found).sum()) - res["counts"]["non_finite_queries"]
+        st["counts"], st["grid"] = res["counts"], res["grid"]
+        if samples:
+            st.update(points=pts, weight=weight, distance=d, face=res["face"])
+        out[name] = st
+        lap(name + ".stats", clock)
+    out["hausdorff"] = max(out["a_to_b"]["max"], out["b_to_a"]["max"]) if not (np.isnan(out["a_to_b"]["max"]) or np.isnan(out["b_to_a"]["max"])) \
+        else float("nan")
+    out["chamfer"] = out["a_to_b"]["mean"] + out["b_to_a"]["mean"]
+    if timing:
+        times.pop("start", None)
+        out["times"] = times
+    return out
+
+
 # faces whose clipped box of samples holds at least this many pixels are walked one wavefront per face (mofa_raster_faces); the choice
 # changes no bit of the frame.  profiles/mesh_raster.md holds the sweep it comes from.
 WAVE_MIN_PIXELS = 64
@@ -913,5 +1191,5 @@ def read_ply(path: str):
     return verts, faces, colors, np.stack([vrec["nx"], vrec["ny"], vrec["nz"]], -1).astype(np.float32).reshape(-1, 3)
 
 
-__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "refine_vertices", "density_normals", "vertex_normals", "components", "select_components", "keep_components", "simplify", "rasterize", "depth_agreement", "to8b", "write_ply",
+__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "refine_vertices", "density_normals", "vertex_normals", "components", "select_components", "keep_components", "simplify", "closest_points", "sample_faces", "surface_distance", "dist_grid", "default_dist_grid", "rasterize", "depth_agreement", "to8b", "write_ply",
                            "read_ply")

@@ -1097,7 +1097,7 @@ class Renderer(torch.nn.Module):
             return occupancy.occupancy_from_grids(grids, threshold, lo, step, dilate)
 
     def extract_mesh(self, network, *, bounds, resolution, level, shapeCodes, expType=20, expCodes=None, uvCodes=None, colors=False,
-                     netchunk=None, brick=None, refine=0, normals=None, components=None, simplify=None, placement="quadric"):
+                     netchunk=None, brick=None, refine=0, normals=None, components=None, simplify=None, placement="quadric", simplify_error=False):
         """Triangle mesh of the face: ``{density >= level}`` over the grid of :meth:`query_density`, by marching tetrahedra on the GPU
         (``mofa_iso_count`` / ``mofa_iso_emit``).  Returns ``(verts [V,3] float32, faces [F,3] int32)`` — watertight, normals
         ``(v1 - v0) x (v2 - v0)`` toward lower density — plus, with ``colors=True`` (needs ``uvCodes``), ``colors [V,3]`` in [0,1]:
@@ -1134,8 +1134,15 @@ class Renderer(torch.nn.Module):
         vertex positions and so run on the fewer vertices (``self.mesh_stats["normal_evaluations"]`` / ``["color_evaluations"]`` count
         them); ``normals="faces"`` is computed on the simplified mesh.  ``self.mesh_stats["simplify"]`` keeps ``mesh.simplify``'s
         statistics.  The result is closed where the input is, but not necessarily manifold.  ``None`` launches nothing and returns the
-        same bytes as before.  What it does to a trained face has not been measured."""
+        same bytes as before.  What it does to a trained face has not been measured.
+
+        ``simplify_error=True`` (needs ``simplify=``) measures what the simplification cost: the surface distance, both ways
+        (``mesh.surface_distance``), between the unsimplified mesh — after ``components=`` and ``refine=`` — and the simplified one, sampled at
+        one grid step (the smallest of the three).  The result goes to ``self.mesh_stats["simplify_error"]``; ``mesh_stats["simplify"]``
+        keeps its shape.  ``False`` launches nothing and adds no key."""
         from . import mesh
+        if simplify_error and simplify is None:
+            raise lib.MofaError("extract_mesh: simplify_error=True measures a simplification; it needs simplify=")
         if simplify is not None and not (isinstance(simplify, (int, np.integer)) and not isinstance(simplify, (bool, np.bool_)) and simplify >= 2):
             raise lib.MofaError(f"extract_mesh: simplify = {simplify!r} (want None or an integer >= 2: grid steps per cell)")
         if placement not in ("quadric", "mean"):
@@ -1176,8 +1183,12 @@ class Renderer(torch.nn.Module):
                     verts, _ = self._refine_mesh(network, verts, faces, res, lo, step, float(level), refine, None, shapeCodes, expType,
                                                  expCodes, netchunk)
                 cell = (np.float32(int(simplify)) * np.asarray(step, dtype=np.float32)).astype(np.float32)
-                verts, faces, self.mesh_stats["simplify"] = mesh.simplify(verts.contiguous(), faces.contiguous(), cell, origin=lo,
-                                                                          placement=placement)
+                full = (verts.contiguous(), faces.contiguous())
+                verts, faces, self.mesh_stats["simplify"] = mesh.simplify(full[0], full[1], cell, origin=lo, placement=placement)
+                if simplify_error:
+                    self.mesh_stats["simplify_error"] = mesh.surface_distance(full[0], full[1], verts, faces,
+                                                                              float(np.min(np.asarray(step, dtype=np.float32))))
+                del full
                 self.mesh_stats.pop("edge_ids", None)
                 if normals is not None:
                     verts, nrm = self._refine_mesh(network, verts, faces, res, lo, step, float(level), 0, normals, shapeCodes, expType,

@@ -29,7 +29,8 @@ the extraction's.  ON SEEDED WEIGHTS THE COMPONENTS SAY NOTHING ABOUT THE FLOATE
 (``mesh.simplify``; ``--placement mean`` is plain clustering, the baseline), after ``--components`` and ``--refine`` and before
 ``--normals`` and ``--colors``; the tool prints the counts before and after and how the representatives were placed.  The result is
 closed where the input is, not necessarily manifold.  What the method does to a trained face has not been measured: seeded weights say
-nothing about it.
+nothing about it.  ``--simplify-error`` measures the surface distance between the unsimplified and the simplified mesh, both ways
+(``mesh.surface_distance`` sampled at one grid step), and prints it; on seeded weights it says nothing about a trained face either.
 """
 import argparse
 import itertools
@@ -117,6 +118,18 @@ def simplify_report(st):
           f"by more than one face (non-manifold there)")
 
 
+def distance_report(err, what="unsimplified -> simplified", back="simplified -> unsimplified"):
+    """The statistics of mesh.surface_distance, one line per direction."""
+    for d, name in (("a_to_b", what), ("b_to_a", back)):
+        e = err[d]
+        print(f"  {name}: mean {e['mean']:.6g}, rms {e['rms']:.6g}, median {e['p50']:.6g}, 95 % {e['p95']:.6g}, max {e['max']:.6g} "
+              f"({e['n_samples']} samples, {e['n_beyond']} beyond the bound; grid {e['grid']}, "
+              f"{e['counts']['candidate_tests'] / max(e['n_samples'], 1):.1f} triangle tests per sample)")
+    print(f"  Hausdorff {err['hausdorff']:.6g}, chamfer (sum of the two means) {err['chamfer']:.6g}")
+    if "times" in err:
+        print("  seconds: " + ", ".join(f"{k} {v:.4f}" for k, v in err["times"].items()))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     src = ap.add_mutually_exclusive_group(required=True)
@@ -144,7 +157,11 @@ def main(argv=None):
                     "(after --components / --refine, before --normals / --colors)")
     ap.add_argument("--placement", choices=("quadric", "mean"), default="quadric", help="with --simplify: the quadric-error representative "
                     "or the cluster mean (plain clustering)")
+    ap.add_argument("--simplify-error", action="store_true", help="with --simplify: measure and print the surface distance between the "
+                    "unsimplified and the simplified mesh (mesh.surface_distance, sampled at one grid step)")
     a = ap.parse_args(argv)
+    if a.simplify_error and a.simplify is None:
+        ap.error("--simplify-error needs --simplify")
     if a.compare_dense and a.simplify is not None:
         ap.error("--compare-dense compares the unsimplified meshes: drop --simplify")
     if a.compare_dense and a.components is not None:
@@ -159,7 +176,8 @@ def main(argv=None):
     res = tuple(a.resolution)
     kw = dict(bounds=bounds, resolution=res, shapeCodes=bm, expType=20, expCodes=exp, netchunk=a.netchunk)
     out = render.extract_mesh(net, level=a.level, uvCodes=uv if a.colors else None, colors=a.colors, brick=a.brick, refine=a.refine,
-                              normals=a.normals, components=a.components, simplify=a.simplify, placement=a.placement, **kw)
+                              normals=a.normals, components=a.components, simplify=a.simplify, placement=a.placement,
+                              simplify_error=a.simplify_error, **kw)
     verts, faces = out[0], out[1]
     mesh.write_ply(a.out, verts, faces, out[2] if a.colors else None, normals=out[-1] if a.normals else None)
     print(f"wrote {a.out}: V = {verts.shape[0]}, F = {faces.shape[0]}")
@@ -173,6 +191,10 @@ def main(argv=None):
         if a.synthetic:
             print("seeded synthetic weights: the simplification below says NOTHING about what the method does to a trained face")
         simplify_report(render.mesh_stats["simplify"])
+        if a.simplify_error:
+            print("surface distance between the unsimplified and the simplified mesh" +
+                  (" (seeded synthetic weights: NOTHING about a trained face)" if a.synthetic else "") + ":")
+            distance_report(render.mesh_stats["simplify_error"])
     if a.normals == "density":
         print(f"density normals: {render.mesh_stats['zero_normals']} of {verts.shape[0]} vertices have a vanishing gradient")
     if a.brick is not None:

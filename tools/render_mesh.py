@@ -12,7 +12,8 @@ what the linear vertex placement contributed to the first number.  ``--component
 are removed before the mesh is rasterised, so a level's agreement can be read with and without them.  ``--simplify M`` extracts every
 level once more with ``extract_mesh(simplify=M)`` (vertex clustering on cells of M grid steps, quadric-error representatives), rasterises
 it from the same pose and prints its agreement with the volume next to the unsimplified mesh's, and the agreement of the simplified mesh
-with the unsimplified one (the unsimplified mesh's mask standing in as ``acc`` with ``acc_min`` 0.5): what the simplification cost in depth.
+with the unsimplified one (the unsimplified mesh's mask standing in as ``acc`` with ``acc_min`` 0.5): what the simplification cost in depth
+from this one camera.  Next to it the surface distance between the two meshes (``mesh.surface_distance``: all of the surface, both ways).
 
 Networks come from a checkpoint (``--ckpt``) or seeded synthetic weights (``--synthetic DC WC DF WF``), codes from ``--fit`` or
 ``synth.codes`` — the options of tools/render_geometry.py.  ON SEEDED WEIGHTS THE AGREEMENT NUMBERS MEAN NOTHING ABOUT A TRAINED FACE:
@@ -149,15 +150,19 @@ def main(argv=None):
                 t0 = time.perf_counter()
                 sv, sf = render.extract_mesh(net, bounds=bounds, resolution=tuple(a.resolution), level=level, shapeCodes=bm, expType=20,
                                              expCodes=exp, netchunk=a.netchunk, brick=a.brick, refine=k, components=a.components,
-                                             simplify=a.simplify)[:2]
+                                             simplify=a.simplify, simplify_error=True)[:2]
                 torch.cuda.synchronize()
                 t_simp = (time.perf_counter() - t0) * 1e3
+                err = render.mesh_stats["simplify_error"]
                 ss = {key: val for key, val in render.mesh_stats["simplify"].items() if key != "cluster_of"}
                 t_smesh, _, (srgb, sdepth, smask, _) = median_ms(lambda: render.render_mesh(H, H, K, pose, sv, sf, znear=a.znear), a.warmup, a.frames)
                 s_vol = mesh.depth_agreement(sdepth, smask, depth_vol, acc, a.acc_min)
                 s_full = mesh.depth_agreement(sdepth, smask, depth, mask.to(torch.float32), 0.5)
                 row["simplified"] = {"simplify": a.simplify, "extract_ms": round(t_simp, 2), "render_mesh_ms": t_smesh, **ss,
-                                     "against_volume": s_vol, "against_unsimplified": s_full}
+                                     "against_volume": s_vol, "against_unsimplified": s_full,
+                                     "surface_distance": {"hausdorff": err["hausdorff"], "chamfer": err["chamfer"],
+                                                          **{d: {q: err[d][q] for q in ("mean", "rms", "max", "p50", "p95", "n_samples")}
+                                                             for d in ("a_to_b", "b_to_a")}}}
                 print(f"  simplify={a.simplify}: V = {ss['verts_out']}, F = {ss['faces_out']} ({ss['faces_in'] / max(ss['faces_out'], 1):.1f}x fewer faces; "
                       f"placed {ss['placed_quadric']} quadric / {ss['placed_mean']} mean / {ss['placed_first']} first vertex, {ss['edges_multiple']} "
                       f"directed edges used twice); extract + simplify {t_simp:.1f} ms, render_mesh {t_smesh:.3f} ms", flush=True)
@@ -165,6 +170,10 @@ def main(argv=None):
                       f"{s_vol['median_abs']:.5f} (unsimplified {agree['median_abs']:.5f}), 95 % {s_vol['p95_abs']:.5f} (unsimplified {agree['p95_abs']:.5f})")
                 print(f"    against the unsimplified mesh: IoU {s_full['iou']:.4f}, |depth difference| median {s_full['median_abs']:.5f}, "
                       f"95 % {s_full['p95_abs']:.5f}", flush=True)
+                print(f"    surface distance (mesh.surface_distance, all of the surface, both ways; included in the {t_simp:.1f} ms): unsimplified -> "
+                      f"simplified mean {err['a_to_b']['mean']:.5f}, 95 % {err['a_to_b']['p95']:.5f}, max {err['a_to_b']['max']:.5f}; simplified -> "
+                      f"unsimplified mean {err['b_to_a']['mean']:.5f}, 95 % {err['b_to_a']['p95']:.5f}, max {err['b_to_a']['max']:.5f}; Hausdorff "
+                      f"{err['hausdorff']:.5f}" + ("  (seeded weights: nothing about a trained face)" if a.synthetic else ""), flush=True)
                 sink.submit(stem + f"_simplify{a.simplify}_mesh.png", srgb)
     print(json.dumps({"size": H, "samples": a.samples, "angle": a.angle, "radius": a.radius, "near": a.near, "far": a.far, "acc_min": a.acc_min,
                       "median_threshold": a.median_threshold, "resolution": a.resolution, "brick": a.brick, "refine": a.refine, "components": a.components,
