@@ -457,6 +457,55 @@ int mofa_dist_sample_count(const float* verts, const int32_t* faces, int64_t F, 
 int mofa_dist_sample_emit(const float* verts, const int32_t* faces, int64_t F, int64_t V, const double* area, const int32_t* k,
                           const int64_t* offsets, const int32_t* face_of, int64_t S, float* points, double* weight, void* stream);
 
+/* Mesh winding numbers: the signed count of the faces of a triangle mesh (verts [V,3] float, faces [F,3] int32) that the ray p + t e_a,
+ * t > 0, of a query p crosses, for N queries through a 2-D grid of face lists (mesh.py drives the passes: mesh.winding_number,
+ * mesh.signed_distance, mesh.surface_distance(signed=True), mesh.inside_grid; 1 <= N, V, F <= 2^31 - 1, axis a = 0, 1 or 2).  For a closed
+ * mesh the count is the winding number of the surface around p: +1 inside a solid whose normals point outward, 0 outside and in a cavity,
+ * 2 inside two overlapping solids, -1 inside an inward-oriented mesh.  No float or double atomics: the same input gives the same bytes every
+ * time; the only atomics are the integer counters counts[MOFA_WIND_COUNTS] (int64, DEVICE, zeroed by the caller).  Every kernel checks the
+ * indices it dereferences: a bad one is skipped.  No kernel waits on another thread.  With u = (a + 1) % 3 and v = (a + 2) % 3 ((u, v, a)
+ * is right-handed), all arithmetic is fp64 on the fp32 coordinates widened, every difference and every product rounded separately (no FMA).
+ *   the face           (X0, X1, X2) against p:
+ *                        1. right_k = X_k.u > p.u.  All three equal: the face is not crossed.
+ *                        2. The edge X_k -> X_k+1 straddles when right_k != right_k+1; L = its non-right endpoint, R = its right one (the
+ *                           same points in the same roles for the two faces of an edge: both compute the same bits).
+ *                             p.v >= max(L.v, R.v): not above;  p.v < min(L.v, R.v): above;  otherwise
+ *                             E = (R.u - L.u) (p.v - L.v) - (R.v - L.v) (p.u - L.u), above = E < 0 (a tie is not above).
+ *                           An edge that is above adds right_k ? +1 : -1 to w.  Zero or two edges straddle: w is -1, 0 or +1.
+ *                        3. Only when w != 0:  p.a < min X_k.a: hit;  p.a >= max X_k.a: no hit;  otherwise ab = X1 - X0, ac = X2 - X0,
+ *                           d = p - X0 (components in x, y, z order whatever the axis), n = (ab.y ac.z - ab.z ac.y, ab.z ac.x - ab.x ac.z,
+ *                           ab.x ac.y - ab.y ac.x), s = (n.x d.x + n.y d.y) + n.z d.z, hit = w > 0 ? s < 0 : s > 0.
+ *                        4. A hit adds w to winding and 1 to crossings.
+ *                      A ray through a shared edge or vertex is decided by the vertex classes and the canonical edge flags alone, which are
+ *                      the same bits in every face that shares it: the count is that of the mesh's slice polygon, right for every query
+ *                      that is not within rounding of the surface itself.
+ *   the grid           n[2] cells (1 .. MOFA_WIND_MAX_GRID per axis) over (u, v) from origin[2] with cell[2] > 0 (HOST arrays of doubles).
+ *                      idx(x) = t >= 0 ? (t < n ? (int) t : n - 1) : 0 with t = floor((x - origin) / cell); cell id = iu n[1] + iv.  A face
+ *                      whose three u or whose three v have no extent (min == max) is FLAT: it enters no cell (it can never be crossed).
+ *                      Every other face enters the cells idx(min u) .. idx(max u) x idx(min v) .. idx(max v).  A face can only count where
+ *                      min u <= p.u < max u and min v <= p.v < max v and idx is monotone: the resolution changes no bit of the result.
+ *   mofa_wind_bin_count    n_cells[f] (int64) = the cells face f enters; counts[MOFA_WIND_FLAT] += the flat faces
+ *   mofa_wind_bin_emit     with offsets [F] (int64, DEVICE) = the exclusive sum of n_cells and P = its total (1 .. 2^31 - 1): pair_cell /
+ *                          pair_face [P] (int32), face f's cells in ascending id from offsets[f].  The caller sorts the pairs stably by cell
+ *                          (each cell's faces then ascend) and forms cell_start [cells + 1] (int32).
+ *   mofa_wind_query        one thread per query; thread i takes query order[i] (int64 [N], DEVICE: a permutation that puts queries of one
+ *                          cell next to each other; NULL = the identity), walks the faces pair_face[cell_start[c] .. cell_start[c + 1] - 1]
+ *                          of the cell c of (idx(p.u), idx(p.v)) in list order and writes winding [N] and crossings [N] (int32).  A query
+ *                          with a non-finite coordinate gets 0 / 0 and is counted in counts[MOFA_WIND_NON_FINITE].
+ *                          counts[MOFA_WIND_TESTS] += the listed faces walked, counts[MOFA_WIND_MAX_COLUMN] = max(the longest list a query
+ *                          walked): both depend on the grid, no result does.  P = 0 (0 .. 2^31 - 1): nothing is listed, cell_start is not
+ *                          read and pair_face may be NULL.
+ * A null pointer, an axis outside 0 .. 2 or a grid out of range returns MOFA_EINVAL with a message. */
+enum { MOFA_WIND_NON_FINITE = 0, MOFA_WIND_FLAT = 1, MOFA_WIND_TESTS = 2, MOFA_WIND_MAX_COLUMN = 3, MOFA_WIND_COUNTS = 4 };
+#define MOFA_WIND_MAX_GRID 4096
+int mofa_wind_bin_count(const float* verts, const int32_t* faces, int64_t F, int64_t V, int32_t axis, const double origin[2], const double cell[2],
+                        const int32_t n[2], int64_t* n_cells, int64_t* counts, void* stream);
+int mofa_wind_bin_emit(const float* verts, const int32_t* faces, int64_t F, int64_t V, int32_t axis, const double origin[2], const double cell[2],
+                       const int32_t n[2], const int64_t* offsets, int64_t P, int32_t* pair_cell, int32_t* pair_face, void* stream);
+int mofa_wind_query(const float* points, int64_t N, const int64_t* order, const float* verts, int64_t V, const int32_t* faces, int64_t F,
+                    int32_t axis, const double origin[2], const double cell[2], const int32_t n[2], const int32_t* cell_start,
+                    const int32_t* pair_face, int64_t P, int32_t* winding, int32_t* crossings, int64_t* counts, void* stream);
+
 /* ---- occupancy-culled rendering: skip the network where an occupancy grid says the space is empty ---------------------------------
  * The grid lives on the lattice of mofa_grid_points (nx x ny x nz samples at lo + (i,j,k) step): (nx-1)(ny-1)(nz-1) cells, one byte
  * each (0 / 1), cell index (i (ny-1) + j) (nz-1) + k.  The lattice needs 2 <= n < 2^24 per axis and fewer than 2^31 cells.

@@ -100,6 +100,9 @@ SIGNATURES = {
                                   _fp, _fp, _fp, _fp, _fp]),
     "mofa_dist_sample_count": (C.c_int, [_fp, _fp, _i64, _i64, C.c_double, _i32, _fp, _fp, _fp]),
     "mofa_dist_sample_emit": (C.c_int, [_fp, _fp, _i64, _i64, _fp, _fp, _fp, _fp, _i64, _fp, _fp, _fp]),
+    "mofa_wind_bin_count": (C.c_int, [_fp, _fp, _i64, _i64, _i32, _d3, _d3, C.POINTER(_i32), _fp, _fp, _fp]),
+    "mofa_wind_bin_emit": (C.c_int, [_fp, _fp, _i64, _i64, _i32, _d3, _d3, C.POINTER(_i32), _fp, _i64, _fp, _fp, _fp]),
+    "mofa_wind_query": (C.c_int, [_fp, _i64, _fp, _fp, _i64, _fp, _i64, _i32, _d3, _d3, C.POINTER(_i32), _fp, _fp, _i64, _fp, _fp, _fp, _fp]),
     "mofa_occ_workspace_bytes": (_sz, [_i64]),
     "mofa_occ_cells": (C.c_int, [_fp, _i64, _i64, _i64, C.c_float, _i32, _fp, _fp]),
     "mofa_occ_dilate": (C.c_int, [_fp, _i64, _i64, _i64, _i32, _fp, _fp, _fp]),

@@ -7,6 +7,7 @@ density normals (``refine_vertices``, ``density_normals``, ``mofa_edge_*`` / ``m
 ``select_components`` / ``keep_components`` drop the floaters among them.
 ``simplify`` clusters a mesh's vertices (``mofa_simp_*``); ``closest_points`` finds the exact closest point of a mesh to every query,
 ``sample_faces`` samples a surface deterministically and ``surface_distance`` measures one mesh against another (``mofa_dist_*``).
+``winding_number`` says which side of a closed mesh a point is on (``mofa_wind_*``); ``signed_distance`` and ``inside_grid`` sit on it.
 
 ``Renderer.query_density`` and ``Renderer.extract_mesh`` are the user-facing entry points; this module holds the pieces they share.
 The mesh is watertight and consistently oriented (normals toward lower density); vertices and faces come out in a fixed order with
@@ -811,8 +812,9 @@ def closest_points(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tenso
     without a launch; ``F == 0``, or only degenerate faces, gives face -1 and distance ``inf`` everywhere.
 
     Raises ``MofaError`` for CPU tensors, wrong dtypes or shapes, a face index outside the mesh (after ``mofa_cc_validate``, before any
-    other kernel), a non-finite target vertex, ``max_distance`` not > 0 and a grid outside 1 .. DIST_GRID_CAP.  No signed distance: a sign
-    taken from the closest face's normal is wrong at edges and vertices."""
+    other kernel), a non-finite target vertex, ``max_distance`` not > 0 and a grid outside 1 .. DIST_GRID_CAP.  The distance has no sign
+    here (one taken from the closest face's normal would be wrong at edges and vertices): :func:`signed_distance` adds it from the mesh's
+    winding number."""
     who = "closest_points"
     V, F, dev = _mesh_tensors(who, verts, faces)
     N = _query_points(who, points, dev)
@@ -958,8 +960,28 @@ def _distance_stats(d: torch.Tensor, weight: torch.Tensor, found: torch.Tensor) 
     return out
 
 
+def _signed_stats(d: torch.Tensor, weight: torch.Tensor, found: torch.Tensor, inside: torch.Tensor) -> dict:
+    """signed_mean / inside_fraction over the samples with a weight, max_inside / max_outside over all of them, of the distances ``d``
+    (float64) that were found; ``inside`` says which of them count as negative."""
+    nan = float("nan")
+    out = {"signed_mean": nan, "inside_fraction": nan, "max_inside": nan, "max_outside": nan}
+    d, weight, inside = d[found], weight[found], inside[found]
+    if bool(inside.any()):
+        out["max_inside"] = float(d[inside].max())
+    if not bool(inside.all()):
+        out["max_outside"] = float(d[~inside].max())
+    keep = weight > 0
+    d, weight, inside = d[keep], weight[keep], inside[keep]
+    total = weight.sum()
+    if d.numel() and float(total) > 0:
+        out["signed_mean"] = float((weight * torch.where(inside, -d, d)).sum() / total)
+        out["inside_fraction"] = float((weight * inside.to(torch.float64)).sum() / total)
+    return out
+
+
 def surface_distance(verts_a: torch.Tensor, faces_a: torch.Tensor, verts_b: torch.Tensor, faces_b: torch.Tensor, spacing: float,
-                     max_distance=None, vertices: bool = True, timing: bool = False, samples: bool = False, max_subdiv: int = 64) -> dict:
+                     max_distance=None, vertices: bool = True, timing: bool = False, samples: bool = False, max_subdiv: int = 64,
+                     signed: bool = False) -> dict:
     """Surface distance between two triangle meshes on the GPU, both ways.  For ``a_to_b``: the quadrature samples of mesh a
     (:func:`sample_faces` with ``spacing`` and ``max_subdiv``) plus, with ``vertices=True``, the vertices a's faces reference with weight 0
     — they count in ``max`` and not in the means: a Hausdorff distance is often attained at a vertex, which no centroid reaches —
@@ -968,7 +990,14 @@ def surface_distance(verts_a: torch.Tensor, faces_a: torch.Tensor, verts_b: torc
     counted) and ``counts`` (closest_points' counters); ``samples=True`` adds ``points``, ``weight``, ``distance`` (fp64, sqrt of ``d2``)
     and ``face``.  The dict also holds ``hausdorff`` (the larger of the two maxima) and ``chamfer`` (the sum of the two means), and with
     ``timing=True`` ``times``: seconds of ``sample``, ``query`` and ``stats`` per direction, each ended by a device synchronisation.
-    A direction without samples, or with every sample beyond the bound, has NaN statistics.  The distances are unsigned."""
+    A direction without samples, or with every sample beyond the bound, has NaN statistics.
+
+    The distances are unsigned unless ``signed=True``: every sample then also goes through :func:`winding_number` of the other mesh (which
+    must be closed: ``MofaError`` otherwise) and each direction additionally carries ``signed_mean`` (area-weighted, fp64, the distance
+    counted negative where the sample lies inside the other mesh), ``inside_fraction`` (the share of the weight that lies inside),
+    ``max_inside`` / ``max_outside`` (the largest distance on either side, the weight-0 vertices included; NaN when a side has no sample),
+    ``open_edges`` of the target mesh (0) and, with ``samples=True``, ``inside``; ``times`` gains ``winding`` per direction.  With
+    ``signed=False`` nothing new is launched and the dict is what it always was."""
     who = "surface_distance"
     _mesh_tensors(who, verts_a, faces_a)
     _mesh_tensors(who, verts_b, faces_b)
@@ -995,6 +1024,13 @@ def surface_distance(verts_a: torch.Tensor, faces_a: torch.Tensor, verts_b: torc
         found = res["face"] >= 0
         d = torch.sqrt(res["d2"])
         st = _distance_stats(d, weight, found)
+        if signed:
+            wind = winding_number(pts, vb, fb)
+            clock = lap(name + ".winding", clock)
+            st.update(_signed_stats(d, weight, found, wind["inside"]))
+            st["open_edges"] = wind["open_edges"]
+            if samples:
+                st["inside"] = wind["inside"]
         st["n_samples"] = int(pts.shape[0])
         st["n_beyond"] = int((~found).sum()) - res["counts"]["non_finite_queries"]
         st["counts"], st["grid"] = res["counts"], res["grid"]
@@ -1009,6 +1045,222 @@ def surface_distance(verts_a: torch.Tensor, faces_a: torch.Tensor, verts_b: torc
         times.pop("start", None)
         out["times"] = times
     return out
+
+
+# winding_number's 2-D grid of face lists over the plane across the ray: cells of about WIND_GRID_FACTOR face sizes (the face size estimated
+# as for closest_points), at most WIND_GRID_AUTO_CAP per axis; WIND_GRID_CAP is the most a caller may force.  The resolution changes no
+# bit of the result; profiles/mesh_winding.md holds what is known about the numbers.
+WIND_GRID_CAP = 2048
+WIND_GRID_AUTO_CAP = 256
+WIND_GRID_FACTOR = 2.0
+_WIND_COUNTS = ("non_finite_queries", "flat_faces", "face_tests", "max_column")       # MOFA_WIND_* of the header
+
+
+def _wind_axes(axis: int):
+    return (axis + 1) % 3, (axis + 2) % 3
+
+
+def wind_grid(lo, hi, n, axis: int = 2):
+    """(origin [2], cell [2]) in float64 of winding_number's grid of ``n = (nu, nv)`` cells over the (u, v) sides of the box ``lo .. hi``
+    (three coordinates each), ``u = (axis + 1) % 3``, ``v = (axis + 2) % 3``: ``cell = extent / n``, 1 on a side of no extent."""
+    uv = list(_wind_axes(int(axis)))
+    origin = np.asarray(lo, dtype=np.float64).reshape(3)[uv]
+    extent = np.asarray(hi, dtype=np.float64).reshape(3)[uv] - origin
+    return origin, np.where(extent > 0, extent / np.asarray(n, dtype=np.float64).reshape(2), 1.0)
+
+
+def default_wind_grid(lo, hi, F: int, axis: int = 2):
+    """The resolution winding_number picks for ``F`` faces in the box ``lo .. hi``: ``ceil(extent / h)`` cells on the u and on the v side,
+    ``h`` = WIND_GRID_FACTOR sqrt(the box's surface area / F), clamped to 1 .. WIND_GRID_AUTO_CAP."""
+    e = np.asarray(hi, dtype=np.float64).reshape(3) - np.asarray(lo, dtype=np.float64).reshape(3)
+    area = 2.0 * (e[0] * e[1] + e[1] * e[2] + e[0] * e[2])
+    if not (F > 0 and area > 0 and np.isfinite(area)):
+        return (1, 1)
+    h = WIND_GRID_FACTOR * np.sqrt(area / F)
+    return tuple(int(v) for v in np.clip(np.ceil(e[list(_wind_axes(int(axis)))] / h), 1, WIND_GRID_AUTO_CAP))
+
+
+def _open_edges(faces: torch.Tensor, V: int) -> int:
+    """The directed edges (a, b) of ``faces`` (validated) with count(a -> b) != count(b -> a); 0 for a closed, consistently oriented mesh."""
+    f = faces.long()
+    key = torch.cat([f[:, 0] * V + f[:, 1], f[:, 1] * V + f[:, 2], f[:, 2] * V + f[:, 0]])
+    uniq, count = torch.unique(key, return_counts=True)
+    back = (uniq % V) * V + torch.div(uniq, V, rounding_mode="floor")
+    at = torch.searchsorted(uniq, back).clamp_(max=uniq.numel() - 1)
+    return int((torch.where(uniq[at] == back, count[at], torch.zeros_like(count)) != count).sum())
+
+
+def _wind_args(who, axis, grid):
+    if isinstance(axis, (bool, np.bool_)) or not isinstance(axis, (int, np.integer)) or not 0 <= int(axis) <= 2:
+        raise lib.MofaError(f"{who}: axis = {axis!r} (want 0, 1 or 2)")
+    if grid is not None:
+        g = np.asarray(grid).reshape(-1)
+        if g.size not in (1, 2) or g.dtype.kind not in "iu" or (g < 1).any() or (g > WIND_GRID_CAP).any():
+            raise lib.MofaError(f"{who}: grid = {grid!r} (want None, an integer or two, 1 .. {WIND_GRID_CAP} per side)")
+        grid = tuple(int(v) for v in (np.repeat(g, 2) if g.size == 1 else g))
+    return int(axis), grid
+
+
+def _wind_lists(who, verts, faces, V, F, axis, grid, require_closed):
+    """Validate the mesh, count its open edges and bin its faces: what every batch of queries against it shares."""
+    L = lib.load()
+    dev = verts.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    stream = lib.stream()
+    bad = torch.zeros(1, **i64)
+    lib.check(L.mofa_cc_validate(faces.data_ptr(), F, V, bad.data_ptr(), stream), "mofa_cc_validate")
+    n_bad = int(bad.cpu()[0])
+    if n_bad:
+        raise lib.MofaError(f"{who}: {n_bad} of the {3 * F} face indices lie outside [0, {V})")
+    bad.zero_()
+    lib.check(L.mofa_dist_validate(lib.ptr(verts), V, bad.data_ptr(), stream), "mofa_dist_validate")
+    n_bad = int(bad.cpu()[0])
+    if n_bad:
+        raise lib.MofaError(f"{who}: {n_bad} of the {3 * V} coordinates of the mesh are not finite")
+    n_open = _open_edges(faces, V)
+    if n_open and require_closed:
+        raise lib.MofaError(f"{who}: the mesh is not closed: {n_open} directed edges have no matching opposite edge (require_closed=False "
+                            "returns the ray's count, which then depends on the axis)")
+    box = torch.stack([verts.amin(0), verts.amax(0)]).cpu().numpy()
+    if grid is None:
+        grid = default_wind_grid(box[0], box[1], F, axis)
+    origin, cell = wind_grid(box[0], box[1], grid, axis)
+    o2, c2, n2 = (C.c_double * 2)(*origin), (C.c_double * 2)(*cell), (C.c_int32 * 2)(*grid)
+    n_cells = grid[0] * grid[1]
+    counts = torch.zeros(len(_WIND_COUNTS), **i64)
+    per_face = torch.empty(F, **i64)
+    lib.check(L.mofa_wind_bin_count(lib.ptr(verts), faces.data_ptr(), F, V, axis, o2, c2, n2, per_face.data_ptr(), counts.data_ptr(), stream),
+              "mofa_wind_bin_count")
+    ends = torch.cumsum(per_face, 0)
+    P = int(ends[-1].cpu())
+    if P > INT32_MAX:
+        raise lib.MofaError(f"{who}: the {F} faces enter {P} cells of the {grid} grid, more than 2^31 - 1: take a coarser grid")
+    start = torch.zeros(n_cells + 1, dtype=torch.int32, device=dev)
+    pair_face = torch.empty(P, dtype=torch.int32, device=dev)
+    if P:
+        offsets = (ends - per_face).contiguous()
+        pair_cell = torch.empty(P, dtype=torch.int32, device=dev)
+        lib.check(L.mofa_wind_bin_emit(lib.ptr(verts), faces.data_ptr(), F, V, axis, o2, c2, n2, offsets.data_ptr(), P, pair_cell.data_ptr(),
+                                       pair_face.data_ptr(), stream), "mofa_wind_bin_emit")
+        if n_cells > 1:
+            by_cell = torch.sort(pair_cell, stable=True).indices
+            pair_face = pair_face[by_cell].contiguous()
+            del by_cell
+        start[1:] = torch.cumsum(torch.bincount(pair_cell.long(), minlength=n_cells), 0).to(torch.int32)
+        del pair_cell, offsets
+    return dict(grid=grid, origin=origin, cell=cell, o2=o2, c2=c2, n2=n2, start=start, pair_face=pair_face, P=P,
+                flat_faces=int(counts.cpu()[_WIND_COUNTS.index("flat_faces")]), open_edges=n_open, axis=axis)
+
+
+def _wind_query(points, N, verts, faces, V, F, b):
+    """(winding [N] int32, crossings [N] int32, counts) of one batch of queries against the lists ``b`` of :func:`_wind_lists`."""
+    L = lib.load()
+    dev = verts.device
+    grid, axis = b["grid"], b["axis"]
+    winding = torch.empty(N, dtype=torch.int32, device=dev)
+    crossings = torch.empty(N, dtype=torch.int32, device=dev)
+    counts = torch.zeros(len(_WIND_COUNTS), dtype=torch.int64, device=dev)
+    order = None
+    if grid[0] * grid[1] > 1:                    # queries of one column next to each other: a wavefront's lanes walk the same list
+        uv = list(_wind_axes(axis))
+        t = torch.nan_to_num((points[:, uv].double() - torch.from_numpy(b["origin"]).to(dev)) / torch.from_numpy(b["cell"]).to(dev), nan=0.0,
+                             posinf=0.0, neginf=0.0).floor_()
+        hi = torch.tensor([g - 1 for g in grid], dtype=torch.float64, device=dev)
+        c = torch.minimum(torch.clamp_(t, min=0.0), hi).long()
+        order = torch.argsort(c[:, 0] * grid[1] + c[:, 1])
+        del t, c
+    lib.check(L.mofa_wind_query(lib.ptr(points), N, None if order is None else order.data_ptr(), lib.ptr(verts), V, faces.data_ptr(), F, axis,
+                                b["o2"], b["c2"], b["n2"], b["start"].data_ptr(), b["pair_face"].data_ptr() if b["P"] else None, b["P"],
+                                winding.data_ptr(), crossings.data_ptr(), counts.data_ptr(), lib.stream()), "mofa_wind_query")
+    c = dict(zip(_WIND_COUNTS, (int(v) for v in counts.cpu())))
+    c["flat_faces"] = b["flat_faces"]
+    return winding, crossings, c
+
+
+def winding_number(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, axis: int = 2, grid=None, require_closed: bool = True) -> dict:
+    """The integer winding number of the closed triangle mesh ``(verts [V,3] float32, faces [F,3] int32)`` around every one of ``points
+    [N,3] float32``, on the GPU (``mofa_wind_*``): the signed count of the faces that the ray from the point along ``+axis`` crosses.
+    Returns a dict: ``winding [N] int32``, ``crossings [N] int32`` (the faces crossed, whatever their sign), ``inside [N] bool``
+    (``winding != 0``), ``counts`` (a dict: ``non_finite_queries``, ``flat_faces``, ``face_tests``, ``max_column``), ``grid`` (the
+    resolution used) and ``open_edges``.
+
+    With the orientation of the extracted meshes (normals toward lower density, a positive signed volume) a point inside a solid has
+    winding +1, one in a cavity of a solid or outside 0, one inside two overlapping solids 2, one inside an inward-oriented mesh -1.  The
+    arithmetic is fixed (include/mofanerf_hip.h): a ray that passes through a vertex or an edge is decided by comparisons that come out the
+    same in every face sharing it, so the count is right for every point that is not within rounding of the surface itself, where the
+    answer is arbitrary.  The faces are binned into a 2-D grid over the plane across the ray and a query tests the faces of its own cell
+    only; the resolution — ``grid``: ``None`` (``default_wind_grid``), an int or a pair, 1 .. WIND_GRID_CAP per side — changes the time
+    but no bit of the result, and ``grid=1`` is brute force through the same kernel.  No float atomics: the same bytes every time.
+
+    ``open_edges`` is the number of directed edges (a, b) whose count differs from that of (b, a): 0 for a closed, consistently oriented
+    mesh.  With ``require_closed=True`` anything else raises ``MofaError`` with the count; with ``False`` the ray's count is returned as it
+    is, and for an open mesh it then depends on ``axis`` (there is no fractional winding number here).  A query with a non-finite
+    coordinate gets 0 and is counted, not refused.  ``N == 0``, ``F == 0`` and ``V == 0`` return without a launch of the library: the
+    winding is then 0 everywhere.
+
+    Raises ``MofaError`` for CPU tensors, wrong dtypes or shapes, an axis outside 0 .. 2, a grid outside 1 .. WIND_GRID_CAP, a face
+    index outside the mesh (after ``mofa_cc_validate``, before any other kernel) and a non-finite vertex."""
+    who = "winding_number"
+    V, F, dev = _mesh_tensors(who, verts, faces)
+    N = _query_points(who, points, dev)
+    axis, grid = _wind_args(who, axis, grid)
+    out = {"winding": torch.zeros(N, dtype=torch.int32, device=dev), "crossings": torch.zeros(N, dtype=torch.int32, device=dev),
+           "inside": torch.zeros(N, dtype=torch.bool, device=dev), "counts": dict.fromkeys(_WIND_COUNTS, 0),
+           "grid": grid if grid is not None else (1, 1), "open_edges": 0}
+    if N == 0:
+        return out
+    if V == 0 or F == 0:
+        out["counts"]["non_finite_queries"] = int((~torch.isfinite(points).all(1)).sum())
+        return out
+    with torch.cuda.device(dev):
+        b = _wind_lists(who, verts, faces, V, F, axis, grid, require_closed)
+        out["winding"], out["crossings"], out["counts"] = _wind_query(points, N, verts, faces, V, F, b)
+    out["inside"] = out["winding"] != 0
+    out["grid"], out["open_edges"] = b["grid"], b["open_edges"]
+    return out
+
+
+def signed_distance(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, grid=None, max_distance=None, axis: int = 2) -> dict:
+    """:func:`closest_points` with a sign from :func:`winding_number`: the dict of ``closest_points(points, verts, faces, grid,
+    max_distance)`` — every key of it with that call's bits — plus ``winding [N] int32``, ``inside [N] bool`` (of the ray along ``axis``)
+    and ``signed_distance [N] float32``: ``-distance`` where the point is inside, ``distance`` elsewhere.  A non-finite query keeps its NaN
+    (and counts as outside); a query beyond ``max_distance`` gets ``-inf`` inside and ``+inf`` outside.  The mesh must be closed
+    (``MofaError`` otherwise).  Within rounding of the surface the sign is arbitrary and the distance is 0 to that rounding."""
+    out = closest_points(points, verts, faces, grid=grid, max_distance=max_distance)
+    wind = winding_number(points, verts, faces, axis=axis)
+    out["winding"], out["inside"] = wind["winding"], wind["inside"]
+    out["signed_distance"] = torch.where(wind["inside"], -out["distance"], out["distance"])
+    return out
+
+
+def inside_grid(verts: torch.Tensor, faces: torch.Tensor, resolution, lo, step, axis: int = 2, chunk: int = 1 << 22) -> torch.Tensor:
+    """``bool [nx, ny, nz]``: which sample points of the lattice ``lo + (i, j, k) * step`` (``grid_points``) lie inside the closed mesh
+    (:func:`winding_number` ``!= 0`` along ``axis``), ``chunk`` points at a time against one binning of the faces: a mesh that was edited,
+    simplified or scanned, back to a volume.  ``occupancy.occupancy_from_grid(inside.float(), 0.5, lo, step, dilate)`` turns the mask
+    into an occupancy grid for the culled renderer: a cell is occupied when one of its eight corners is inside.  What that grid misses are
+    parts of the mesh thinner than a cell that hold no lattice point; ``dilate >= 1`` covers those next to an occupied cell, nothing covers
+    a thin part on its own.  A mesh that is not closed raises ``MofaError``; an empty one gives all ``False``."""
+    who = "inside_grid"
+    V, F, dev = _mesh_tensors(who, verts, faces)
+    axis, _ = _wind_args(who, axis, None)
+    res = tuple(int(n) for n in resolution)
+    if len(res) != 3 or min(res) < 1 or res[0] * res[1] * res[2] > INT32_MAX:
+        raise lib.MofaError(f"{who}: resolution = {resolution!r} (want three positive sizes, fewer than 2^31 points in all)")
+    chunk = int(chunk)
+    if chunk < 1:
+        raise lib.MofaError(f"{who}: chunk = {chunk} (want >= 1)")
+    total = res[0] * res[1] * res[2]
+    inside = torch.zeros(total, dtype=torch.bool, device=dev)
+    if V == 0 or F == 0:
+        return inside.reshape(res)
+    with torch.cuda.device(dev):
+        b = _wind_lists(who, verts, faces, V, F, axis, None, True)
+        pts = torch.empty(min(chunk, total), 3, dtype=torch.float32, device=dev)
+        for first in range(0, total, chunk):
+            n = min(chunk, total - first)
+            grid_points(res, lo, step, first, n, pts[:n])
+            inside[first:first + n] = _wind_query(pts[:n], n, verts, faces, V, F, b)[0] != 0
+    return inside.reshape(res)
 
 
 # faces whose clipped box of samples holds at least this many pixels are walked one wavefront per face (mofa_raster_faces); the choice
@@ -1191,5 +1443,6 @@ def read_ply(path: str):
     return verts, faces, colors, np.stack([vrec["nx"], vrec["ny"], vrec["nz"]], -1).astype(np.float32).reshape(-1, 3)
 
 
-__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "refine_vertices", "density_normals", "vertex_normals", "components", "select_components", "keep_components", "simplify", "closest_points", "sample_faces", "surface_distance", "dist_grid", "default_dist_grid", "rasterize", "depth_agreement", "to8b", "write_ply",
+__all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "refine_vertices", "density_normals", "vertex_normals", "components", "select_components", "keep_components", "simplify", "closest_points", "sample_faces", "surface_distance", "dist_grid", "default_dist_grid", "winding_number", "signed_distance",
+                           "inside_grid", "wind_grid", "default_wind_grid", "rasterize", "depth_agreement", "to8b", "write_ply",
                            "read_ply")
