@@ -506,6 +506,41 @@ int mofa_wind_query(const float* points, int64_t N, const int64_t* order, const 
                     int32_t axis, const double origin[2], const double cell[2], const int32_t n[2], const int32_t* cell_start,
                     const int32_t* pair_face, int64_t P, int32_t* winding, int32_t* crossings, int64_t* counts, void* stream);
 
+/* Mesh smoothing: Taubin lambda | mu filtering of the vertices of a triangle mesh (verts [V,3] float, faces [F,3] int32) over a fixed-order
+ * vertex adjacency (mesh.py drives the passes: mesh.vertex_adjacency, mesh.smooth; 1 <= V, F, E <= 2^31 - 1).  No float or double atomics and
+ * a fixed summation order: the same input gives the same bytes every time; the only atomics are the integer counters
+ * counts[MOFA_SMOOTH_COUNTS] (int64, DEVICE, zeroed by the caller).  Every kernel checks the indices it dereferences: a bad one is counted in
+ * counts[MOFA_SMOOTH_BAD_INDEX] and skipped.  No kernel waits on another thread.  All arithmetic is fp64 on the fp32 coordinates widened,
+ * every operation rounded separately (no FMA).
+ *   the adjacency      half-edge entry e = 2 (3 f + c) + dir, c = 0 .. 2, carries the directed pair (a, b) for dir = 0 and (b, a) for dir = 1
+ *                      with a = faces[f][(c + 1) % 3], b = faces[f][(c + 2) % 3] (the edge opposite corner c).  The caller drops the entries
+ *                      with a == b, sorts the rest stably by the key (i << 31) | j — perm [P] (int64) holds the sorted entries' e, ascending
+ *                      inside a run of equal keys — and forms seg [E + 1] (int64), the run boundaries of the E distinct pairs; nbr [E]
+ *                      (int32) = j of every pair and offsets [V + 1] (int64) = the first pair of every i.
+ *   mofa_smooth_corner_cots   cots [F,3] (double): for corner c of face f with apex o = faces[f][c] and a, b as above,
+ *                               u = x_a - x_o, v = x_b - x_o;  cr = (uy vz - uz vy, uz vx - ux vz, ux vy - uy vx);
+ *                               n = sqrt((crx crx + cry cry) + crz crz);  cots[3 f + c] = ((ux vx + uy vy) + uz vz) / n
+ *                             n == 0 or not finite: cots = 0 and counts[MOFA_SMOOTH_FLAT_CORNERS] += 1.
+ *   mofa_smooth_edge_weights  weights [E] (double), one thread per pair p:  w = 0.0;  for k = seg[p] .. seg[p + 1] - 1 in that order:
+ *                             w += 0.5 * cots[perm[k] / 2];  then w < 0: w = 0 and counts[MOFA_SMOOTH_NEGATIVE_WEIGHTS] += 1.  The runs of
+ *                             (i, j) and (j, i) hold the same corners in the same order: w_ij == w_ji bit for bit.  F is that of cots.
+ *   mofa_smooth_step          one thread per vertex i, its neighbours j = nbr[k], k = offsets[i] .. offsets[i + 1] - 1, in that order, per
+ *                             component x:
+ *                               weights == NULL:  s = 0.0;  s += (double)x_j - (double)x_i;  L = s / (double)(offsets[i + 1] - offsets[i])
+ *                               weights [E]:      s = 0.0, sw = 0.0;  s += weights[k] * ((double)x_j - (double)x_i), sw += weights[k];
+ *                                                 sw > 0: L = s / sw; otherwise the vertex keeps its bits, counts[MOFA_SMOOTH_ZERO_WEIGHT] += 1
+ *                               verts_out = (float)((double)x_i + factor * L)
+ *                             A vertex with pinned[i] != 0 (uint8 [V]; NULL: none) or without neighbours keeps its bits.  A vertex with a
+ *                             neighbour outside [0, V) or a list outside [0, E) writes nothing and is counted.  verts_in != verts_out: the
+ *                             step never runs in place; the caller alternates two buffers. */
+enum { MOFA_SMOOTH_FLAT_CORNERS = 0, MOFA_SMOOTH_NEGATIVE_WEIGHTS = 1, MOFA_SMOOTH_ZERO_WEIGHT = 2, MOFA_SMOOTH_BAD_INDEX = 3,
+       MOFA_SMOOTH_COUNTS = 4 };
+int mofa_smooth_corner_cots(const float* verts, const int32_t* faces, int64_t F, int64_t V, double* cots, int64_t* counts, void* stream);
+int mofa_smooth_edge_weights(const double* cots, int64_t F, const int64_t* perm, int64_t P, const int64_t* seg, int64_t E, double* weights,
+                             int64_t* counts, void* stream);
+int mofa_smooth_step(const float* verts_in, int64_t V, const int64_t* offsets, const int32_t* nbr, int64_t E, const double* weights,
+                     const uint8_t* pinned, double factor, float* verts_out, int64_t* counts, void* stream);
+
 /* ---- occupancy-culled rendering: skip the network where an occupancy grid says the space is empty ---------------------------------
  * The grid lives on the lattice of mofa_grid_points (nx x ny x nz samples at lo + (i,j,k) step): (nx-1)(ny-1)(nz-1) cells, one byte
  * each (0 / 1), cell index (i (ny-1) + j) (nz-1) + k.  The lattice needs 2 <= n < 2^24 per axis and fewer than 2^31 cells.

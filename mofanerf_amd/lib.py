@@ -103,6 +103,9 @@ SIGNATURES = {
     "mofa_wind_bin_count": (C.c_int, [_fp, _fp, _i64, _i64, _i32, _d3, _d3, C.POINTER(_i32), _fp, _fp, _fp]),
     "mofa_wind_bin_emit": (C.c_int, [_fp, _fp, _i64, _i64, _i32, _d3, _d3, C.POINTER(_i32), _fp, _i64, _fp, _fp, _fp]),
     "mofa_wind_query": (C.c_int, [_fp, _i64, _fp, _fp, _i64, _fp, _i64, _i32, _d3, _d3, C.POINTER(_i32), _fp, _fp, _i64, _fp, _fp, _fp, _fp]),
+    "mofa_smooth_corner_cots": (C.c_int, [_fp, _fp, _i64, _i64, _fp, _fp, _fp]),
+    "mofa_smooth_edge_weights": (C.c_int, [_fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp]),
+    "mofa_smooth_step": (C.c_int, [_fp, _i64, _fp, _fp, _i64, _fp, _fp, C.c_double, _fp, _fp, _fp]),
     "mofa_occ_workspace_bytes": (_sz, [_i64]),
     "mofa_occ_cells": (C.c_int, [_fp, _i64, _i64, _i64, C.c_float, _i32, _fp, _fp]),
     "mofa_occ_dilate": (C.c_int, [_fp, _i64, _i64, _i64, _i32, _fp, _fp, _fp]),

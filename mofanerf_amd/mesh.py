@@ -8,6 +8,7 @@ density normals (``refine_vertices``, ``density_normals``, ``mofa_edge_*`` / ``m
 ``simplify`` clusters a mesh's vertices (``mofa_simp_*``); ``closest_points`` finds the exact closest point of a mesh to every query,
 ``sample_faces`` samples a surface deterministically and ``surface_distance`` measures one mesh against another (``mofa_dist_*``).
 ``winding_number`` says which side of a closed mesh a point is on (``mofa_wind_*``); ``signed_distance`` and ``inside_grid`` sit on it.
+``vertex_adjacency`` lists every vertex's neighbours in a fixed order and ``smooth`` filters the vertices over it (Taubin, ``mofa_smooth_*``).
 
 ``Renderer.query_density`` and ``Renderer.extract_mesh`` are the user-facing entry points; this module holds the pieces they share.
 The mesh is watertight and consistently oriented (normals toward lower density); vertices and faces come out in a fixed order with
@@ -1263,6 +1264,205 @@ def inside_grid(verts: torch.Tensor, faces: torch.Tensor, resolution, lo, step, 
     return inside.reshape(res)
 
 
+SMOOTH_MAX_ITERATIONS = 1000
+_SMOOTH_COUNTS = ("flat_corners", "negative_weights", "zero_weight", "bad_index")       # MOFA_SMOOTH_* of the header
+_SMOOTH_WEIGHTS = ("uniform", "cotangent")
+_SMOOTH_BOUNDARIES = ("fixed", "free")
+
+
+def _adjacency(who, faces, V, F):
+    """The sorted half-edge entries of a mesh (V, F >= 1; ``mofa_cc_validate`` first) and what follows from them: ``perm [P] int64`` (the
+    entries ``e = 2 (3 f + c) + dir`` without self-loops, stably sorted by the key ``(i << 31) | j``), ``seg [E+1] int64`` (the runs of the
+    E distinct directed pairs), ``offsets``, ``neighbours``, ``boundary`` and, as tensors not yet read, ``degree_max`` and
+    ``edges_nonmanifold``."""
+    dev = faces.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    bad = torch.zeros(1, **i64)
+    lib.check(lib.load().mofa_cc_validate(faces.data_ptr(), F, V, bad.data_ptr(), lib.stream()), "mofa_cc_validate")
+    n_bad = int(bad.cpu()[0])
+    if n_bad:
+        raise lib.MofaError(f"{who}: {n_bad} of the {3 * F} face indices lie outside [0, {V})")
+    f = faces.long()
+    a, b = f[:, [1, 2, 0]], f[:, [2, 0, 1]]                                  # corner c: the edge opposite to it
+    i, j = torch.stack([a, b], -1).reshape(-1), torch.stack([b, a], -1).reshape(-1)       # entry e = 2 (3 f + c) + dir
+    entry = torch.nonzero(i != j)[:, 0]
+    key = (i[entry] << 31) | j[entry]
+    order = torch.sort(key, stable=True).indices
+    perm = entry[order].contiguous()
+    pair, run = torch.unique_consecutive(key[order], return_counts=True)
+    seg = torch.zeros(pair.shape[0] + 1, **i64)
+    seg[1:] = torch.cumsum(run, 0)
+    pi, pj = pair >> 31, pair & INT32_MAX
+    degree = torch.bincount(pi, minlength=V)
+    offsets = torch.zeros(V + 1, **i64)
+    offsets[1:] = torch.cumsum(degree, 0)
+    boundary = torch.zeros(V, dtype=torch.bool, device=dev)
+    boundary[pi[run == 1]] = True                                           # (the pair (j, i) has the same run: both ends are marked)
+    return {"offsets": offsets, "neighbours": pj.to(torch.int32).contiguous(), "boundary": boundary, "perm": perm, "seg": seg,
+            "degree_max": degree.max(), "edges_nonmanifold": ((run > 2) & (pi < pj)).sum(), "n_isolated": (degree == 0).sum()}
+
+
+def vertex_adjacency(faces: torch.Tensor, V: int) -> dict:
+    """The vertex adjacency of the triangle mesh ``faces [F,3] int32`` over ``V`` vertices, in the fixed order :func:`smooth` sums in:
+    ``offsets [V+1] int64`` and ``neighbours [E] int32`` (the neighbours of vertex i are ``neighbours[offsets[i]:offsets[i+1]]``: distinct,
+    ascending, symmetric, no self-loops; a degenerate face ``(a, a, b)`` still makes a and b neighbours), ``degree_max`` (int),
+    ``boundary [V] bool`` (a vertex on an undirected edge that exactly one face side uses: the uses of {i, j} are counted over both
+    directions, a duplicated face counts twice and ``(a, a, b)`` uses {a, b} twice) and ``edges_nonmanifold`` (the undirected edges with
+    more than two uses).  Built from a stable sort of the 6 F half-edge entries by ``(i << 31) | j``.
+
+    The faces are validated first (``mofa_cc_validate``, one host read): an index outside [0, V) raises ``MofaError`` before anything else
+    runs; so do CPU tensors.  ``V == 0`` or ``F == 0`` gives an empty adjacency without a launch."""
+    who = "vertex_adjacency"
+    if not torch.is_tensor(faces) or not faces.is_cuda:
+        raise lib.MofaError(f"{who}: the HIP path needs tensors on the GPU (got CPU faces); there is no CPU fallback")
+    if faces.dtype != torch.int32 or not faces.is_contiguous() or faces.dim() != 2 or faces.shape[1] != 3:
+        raise lib.MofaError(f"{who}: want contiguous int32 faces [F,3], got {faces.dtype} {tuple(faces.shape)} contiguous={faces.is_contiguous()}")
+    if isinstance(V, (bool, np.bool_)) or not isinstance(V, (int, np.integer)) or not 0 <= int(V) <= INT32_MAX:
+        raise lib.MofaError(f"{who}: V = {V!r} (want an integer 0 .. 2^31 - 1)")
+    V, F, dev = int(V), int(faces.shape[0]), faces.device
+    if F > INT32_MAX:
+        raise lib.MofaError(f"{who}: {F} faces exceed the int32 indices (2^31 - 1)")
+    if V == 0 or F == 0:
+        return {"offsets": torch.zeros(V + 1, dtype=torch.int64, device=dev), "neighbours": torch.zeros(0, dtype=torch.int32, device=dev),
+                "degree_max": 0, "boundary": torch.zeros(V, dtype=torch.bool, device=dev), "edges_nonmanifold": 0}
+    with torch.cuda.device(dev):
+        adj = _adjacency(who, faces, V, F)
+        degree_max, nonmanifold = (int(v) for v in torch.stack([adj["degree_max"], adj["edges_nonmanifold"]]).cpu())
+    return {"offsets": adj["offsets"], "neighbours": adj["neighbours"], "degree_max": degree_max, "boundary": adj["boundary"],
+            "edges_nonmanifold": nonmanifold}
+
+
+def _smooth_args(who, iterations, lam, mu, weights, boundary):
+    """smooth's parameters, checked before anything touches the GPU: (iterations, lam, mu or None)."""
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or not 0 <= int(iterations) <= SMOOTH_MAX_ITERATIONS:
+        raise lib.MofaError(f"{who}: iterations = {iterations!r} (want an integer 0 .. {SMOOTH_MAX_ITERATIONS})")
+    try:
+        lam = float(lam)
+        mu = None if mu is None else float(mu)
+    except (TypeError, ValueError):
+        raise lib.MofaError(f"{who}: lam = {lam!r}, mu = {mu!r} (want numbers; mu may be None)") from None
+    if not 0.0 < lam <= 1.0:                                                  # (NaN fails both comparisons)
+        raise lib.MofaError(f"{who}: lam = {lam} (want 0 < lam <= 1)")
+    if mu is not None:
+        if not (mu < -lam and np.isfinite(mu)):
+            raise lib.MofaError(f"{who}: mu = {mu} (want None for plain Laplacian smoothing, or a finite mu < -lam = {-lam})")
+        top = (1.0 - 2.0 * lam) * (1.0 - 2.0 * mu)
+        if top < -1.0:
+            raise lib.MofaError(f"{who}: lam = {lam}, mu = {mu} amplify the top frequency: (1 - 2 lam) (1 - 2 mu) = {top} < -1 (the "
+                                "normalised operator's spectrum is [0, 2])")
+    if weights not in _SMOOTH_WEIGHTS:
+        raise lib.MofaError(f"{who}: weights = {weights!r} (want 'uniform' or 'cotangent')")
+    if boundary not in _SMOOTH_BOUNDARIES:
+        raise lib.MofaError(f"{who}: boundary = {boundary!r} (want 'fixed' or 'free')")
+    return int(iterations), lam, mu
+
+
+def smooth(verts: torch.Tensor, faces: torch.Tensor, iterations: int = 10, lam: float = 0.5, mu: Optional[float] = -0.53,
+           weights: str = "uniform", boundary: str = "fixed", pinned: Optional[torch.Tensor] = None, timing: bool = False):
+    """Taubin lambda | mu smoothing of a triangle mesh's vertices on the GPU (``mofa_smooth_*``): every iteration is a Laplacian step
+    ``x += lam L(x)`` followed by one with ``mu < -lam``, a low-pass filter with the transfer function ``(1 - lam k)(1 - mu k)`` over the
+    normalised Laplacian's spectrum k in [0, 2] that does not shrink the surface the way plain Laplacian smoothing does.  ``mu=None`` is
+    that plain smoothing, one step per iteration: the shrinking baseline.  The defaults are Taubin's published pair, not a tuned one.
+
+    ``L(x)_i`` is the weighted mean of ``x_j - x_i`` over the neighbours j of i in :func:`vertex_adjacency`'s order.  ``weights="uniform"``
+    weighs them equally; ``"cotangent"`` uses ``w_ij = max(0, sum of 0.5 cot(the angle opposite {i, j}))``, computed once on the input
+    positions (clamped, so that an obtuse pair cannot push a vertex away; frozen, so that the filter stays linear).  All sums are fp64 in a
+    fixed order with every operation rounded separately (include/mofanerf_hip.h states them line for line), each step rounds to fp32 once,
+    and there is no float atomic: the same mesh gives the same bytes every time.  ``boundary="fixed"`` pins the boundary vertices of
+    :func:`vertex_adjacency`, ``"free"`` lets them move (an open border then shrinks inward); ``pinned [V] bool`` is OR-ed in.  A pinned
+    vertex, a vertex without neighbours and, with cotangent weights, one whose weights sum to zero keep their bits.  ``faces`` is never
+    touched: numbering and topology stay, and the input tensors are not written.
+
+    Returns ``(verts' [V,3] float32, stats)``; ``stats``: ``passes`` (steps run), ``n_pinned``, ``n_boundary``, ``n_isolated`` (vertices
+    without neighbours), ``degree_max``, ``edges_nonmanifold``, ``flat_corners`` (corners whose cotangent was set to 0), ``negative_weights``
+    (directed pairs clamped), ``zero_weight`` (the last pass's vertices kept for a zero weight sum), ``displacement [V] float32`` (|out - in|
+    from fp64) and ``max_displacement`` and, with ``timing=True``, ``times`` (seconds of the ``adjacency``, ``weights``, ``passes`` and
+    ``stats`` phases, each ended by a device synchronisation).
+
+    Raises ``MofaError`` — before anything touches the GPU — for ``iterations`` not an integer in 0 .. 1000, ``lam`` outside (0, 1], ``mu``
+    not ``None`` and not below ``-lam``, a pair with ``(1 - 2 lam)(1 - 2 mu) < -1`` (it would amplify the top frequency) and unknown
+    ``weights`` / ``boundary``; then for CPU tensors, a face index outside the mesh (after ``mofa_cc_validate``, before any other kernel)
+    and a non-finite vertex some face references.  ``iterations=0``, ``V == 0`` or ``F == 0`` return the input's bits without a launch of
+    the library (and statistics of zeros).  Smoothing moves vertices off the surface they were extracted from; what it does to a trained
+    face has not been measured."""
+    who = "smooth"
+    iterations, lam, mu = _smooth_args(who, iterations, lam, mu, weights, boundary)
+    V, F, dev = _mesh_tensors(who, verts, faces)
+    if pinned is not None and (not torch.is_tensor(pinned) or pinned.dtype != torch.bool or pinned.shape != (V,) or pinned.device != dev):
+        raise lib.MofaError(f"{who}: want pinned = None or a bool mask [{V}] on {dev}")
+    passes = iterations * (1 if mu is None else 2)
+    stats = dict.fromkeys(("passes", "n_pinned", "n_boundary", "n_isolated", "degree_max", "edges_nonmanifold", "flat_corners",
+                           "negative_weights", "zero_weight"), 0)
+    stats.update(displacement=torch.zeros(V, dtype=torch.float32, device=dev), max_displacement=0.0)
+    if iterations == 0 or V == 0 or F == 0:
+        return verts.clone(), stats
+    L = lib.load()
+    times, clock = {}, [time.perf_counter()]
+
+    def lap(phase):
+        if timing:
+            torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            times[phase] = now - clock[0]
+            clock[0] = now
+
+    with torch.cuda.device(dev):
+        stream = lib.stream()
+        lap("start")
+        adj = _adjacency(who, faces, V, F)
+        referenced = torch.zeros(V, dtype=torch.bool, device=dev)
+        referenced[faces.reshape(-1).long()] = True
+        pin = adj["boundary"].clone() if boundary == "fixed" else torch.zeros(V, dtype=torch.bool, device=dev)
+        if pinned is not None:
+            pin |= pinned
+        head = torch.stack([(referenced & ~torch.isfinite(verts).all(1)).sum(), pin.sum(), adj["boundary"].sum(), adj["n_isolated"],
+                            adj["degree_max"], adj["edges_nonmanifold"]]).cpu()
+        n_bad, stats["n_pinned"], stats["n_boundary"], stats["n_isolated"], stats["degree_max"], stats["edges_nonmanifold"] = (int(v) for v in head)
+        if n_bad:
+            raise lib.MofaError(f"{who}: {n_bad} of the vertices the faces reference have a non-finite coordinate")
+        offsets, nbr, perm, seg = adj["offsets"], adj["neighbours"], adj["perm"], adj["seg"]
+        E, P = int(nbr.shape[0]), int(perm.shape[0])
+        lap("adjacency")
+        if E == 0:                                                            # (every face is of the form (a, a, a): nobody has a neighbour)
+            if timing:
+                times.pop("start")
+                stats["times"] = times
+            return verts.clone(), stats
+        counts = torch.zeros(passes + 1, len(_SMOOTH_COUNTS), dtype=torch.int64, device=dev)      # row 0: the weights; row 1 + p: pass p
+        w = None
+        if weights == "cotangent":
+            cots = torch.empty(F, 3, dtype=torch.float64, device=dev)
+            lib.check(L.mofa_smooth_corner_cots(lib.ptr(verts), faces.data_ptr(), F, V, cots.data_ptr(), counts.data_ptr(), stream),
+                      "mofa_smooth_corner_cots")
+            w = torch.empty(E, dtype=torch.float64, device=dev)
+            lib.check(L.mofa_smooth_edge_weights(cots.data_ptr(), F, perm.data_ptr(), P, seg.data_ptr(), E, w.data_ptr(), counts.data_ptr(),
+                                                 stream), "mofa_smooth_edge_weights")
+        lap("weights")
+        pin8 = pin.to(torch.uint8) if (boundary == "fixed" or pinned is not None) else None
+        bufs = (torch.empty_like(verts), torch.empty_like(verts))             # the input is read by the first pass only, never written
+        src = verts
+        for p in range(passes):
+            dst = bufs[p % 2]
+            lib.check(L.mofa_smooth_step(lib.ptr(src), V, offsets.data_ptr(), nbr.data_ptr(), E, None if w is None else w.data_ptr(),
+                                         None if pin8 is None else pin8.data_ptr(), lam if (mu is None or p % 2 == 0) else mu, lib.ptr(dst),
+                                         counts.data_ptr() + 8 * len(_SMOOTH_COUNTS) * (p + 1), stream), "mofa_smooth_step")
+            src = dst
+        lap("passes")
+        c = counts.cpu().numpy()                                              # the counters, read once
+        n_bad = int(c[:, _SMOOTH_COUNTS.index("bad_index")].sum())
+        if n_bad:
+            raise lib.MofaError(f"{who}: {n_bad} indices were out of range inside the passes (the mesh changed while it was smoothed?)")
+        d = src.double() - verts.double()
+        stats["displacement"] = torch.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).float()
+        stats["max_displacement"] = float(stats["displacement"].max())
+        lap("stats")
+    stats.update(passes=passes, flat_corners=int(c[0, 0]), negative_weights=int(c[0, 1]), zero_weight=int(c[passes, 2]))
+    if timing:
+        times.pop("start")
+        stats["times"] = times
+    return src, stats
+
+
 # faces whose clipped box of samples holds at least this many pixels are walked one wavefront per face (mofa_raster_faces); the choice
 # changes no bit of the frame.  profiles/mesh_raster.md holds the sweep it comes from.
 WAVE_MIN_PIXELS = 64
@@ -1444,5 +1644,5 @@ def read_ply(path: str):
 
 
 __all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "refine_vertices", "density_normals", "vertex_normals", "components", "select_components", "keep_components", "simplify", "closest_points", "sample_faces", "surface_distance", "dist_grid", "default_dist_grid", "winding_number", "signed_distance",
-                           "inside_grid", "wind_grid", "default_wind_grid", "rasterize", "depth_agreement", "to8b", "write_ply",
+                           "inside_grid", "wind_grid", "default_wind_grid", "vertex_adjacency", "smooth", "rasterize", "depth_agreement", "to8b", "write_ply",
                            "read_ply")

@@ -1097,7 +1097,8 @@ class Renderer(torch.nn.Module):
             return occupancy.occupancy_from_grids(grids, threshold, lo, step, dilate)
 
     def extract_mesh(self, network, *, bounds, resolution, level, shapeCodes, expType=20, expCodes=None, uvCodes=None, colors=False,
-                     netchunk=None, brick=None, refine=0, normals=None, components=None, simplify=None, placement="quadric", simplify_error=False):
+                     netchunk=None, brick=None, refine=0, normals=None, components=None, simplify=None, placement="quadric", simplify_error=False,
+                     smooth=None, smooth_weights="uniform"):
         """Triangle mesh of the face: ``{density >= level}`` over the grid of :meth:`query_density`, by marching tetrahedra on the GPU
         (``mofa_iso_count`` / ``mofa_iso_emit``).  Returns ``(verts [V,3] float32, faces [F,3] int32)`` — watertight, normals
         ``(v1 - v0) x (v2 - v0)`` toward lower density — plus, with ``colors=True`` (needs ``uvCodes``), ``colors [V,3]`` in [0,1]:
@@ -1139,8 +1140,21 @@ class Renderer(torch.nn.Module):
         ``simplify_error=True`` (needs ``simplify=``) measures what the simplification cost: the surface distance, both ways
         (``mesh.surface_distance``), between the unsimplified mesh — after ``components=`` and ``refine=`` — and the simplified one, sampled at
         one grid step (the smallest of the three).  The result goes to ``self.mesh_stats["simplify_error"]``; ``mesh_stats["simplify"]``
-        keeps its shape.  ``False`` launches nothing and adds no key."""
+        keeps its shape.  ``False`` launches nothing and adds no key.
+
+        ``smooth=n`` (an integer >= 1) runs ``n`` iterations of Taubin smoothing over the vertices (``mesh.smooth`` with its defaults:
+        lam 0.5, mu -0.53, the boundary fixed; ``smooth_weights`` is ``"uniform"`` or ``"cotangent"``): a low-pass filter for the
+        lattice-shaped staircase noise of the extraction.  It runs after ``components=``, ``refine=`` and ``simplify=`` and before
+        ``normals=`` and ``colors=``, which are evaluated at vertex positions and so see the smoothed ones.  Smoothing moves vertices OFF
+        the level set, and ``refine`` cannot run after it (it needs the vertices on their lattice edges: the ``edge_ids`` entry of
+        ``self.mesh_stats`` is dropped, as after ``simplify=``).  Faces and numbering stay.  ``self.mesh_stats["smooth"]`` keeps
+        ``mesh.smooth``'s statistics.  ``None`` launches nothing, adds no key and returns the same bytes as before.  What it does to a
+        trained face has not been measured."""
         from . import mesh
+        if smooth is not None and not (isinstance(smooth, (int, np.integer)) and not isinstance(smooth, (bool, np.bool_)) and smooth >= 1):
+            raise lib.MofaError(f"extract_mesh: smooth = {smooth!r} (want None or an integer >= 1: Taubin iterations)")
+        if smooth_weights not in ("uniform", "cotangent"):
+            raise lib.MofaError(f"extract_mesh: smooth_weights = {smooth_weights!r} (want 'uniform' or 'cotangent')")
         if simplify_error and simplify is None:
             raise lib.MofaError("extract_mesh: simplify_error=True measures a simplification; it needs simplify=")
         if simplify is not None and not (isinstance(simplify, (int, np.integer)) and not isinstance(simplify, (bool, np.bool_)) and simplify >= 2):
@@ -1165,7 +1179,7 @@ class Renderer(torch.nn.Module):
             grid = self.query_density(network, bounds=bounds, resolution=resolution, shapeCodes=shapeCodes, expType=expType,
                                       expCodes=expCodes, netchunk=netchunk)
         with torch.no_grad():
-            if brick is None and not extra and components is None and simplify is None:
+            if brick is None and not extra and components is None and simplify is None and smooth is None:
                 verts, faces = mesh.iso_surface(grid, float(level), lo, step)
             elif brick is None:
                 verts, faces, edge_ids = mesh.iso_surface(grid, float(level), lo, step, edge_ids=True)
@@ -1178,17 +1192,21 @@ class Renderer(torch.nn.Module):
                 verts, faces, self.mesh_stats["edge_ids"] = mesh.keep_components(verts, faces, stats, stats["kept"], self.mesh_stats["edge_ids"])
                 self.mesh_stats["components"] = stats
             nrm = None
-            if simplify is not None:
+            if simplify is not None or smooth is not None:
                 if refine:
                     verts, _ = self._refine_mesh(network, verts, faces, res, lo, step, float(level), refine, None, shapeCodes, expType,
                                                  expCodes, netchunk)
-                cell = (np.float32(int(simplify)) * np.asarray(step, dtype=np.float32)).astype(np.float32)
-                full = (verts.contiguous(), faces.contiguous())
-                verts, faces, self.mesh_stats["simplify"] = mesh.simplify(full[0], full[1], cell, origin=lo, placement=placement)
-                if simplify_error:
-                    self.mesh_stats["simplify_error"] = mesh.surface_distance(full[0], full[1], verts, faces,
-                                                                              float(np.min(np.asarray(step, dtype=np.float32))))
-                del full
+                if simplify is not None:
+                    cell = (np.float32(int(simplify)) * np.asarray(step, dtype=np.float32)).astype(np.float32)
+                    full = (verts.contiguous(), faces.contiguous())
+                    verts, faces, self.mesh_stats["simplify"] = mesh.simplify(full[0], full[1], cell, origin=lo, placement=placement)
+                    if simplify_error:
+                        self.mesh_stats["simplify_error"] = mesh.surface_distance(full[0], full[1], verts, faces,
+                                                                                  float(np.min(np.asarray(step, dtype=np.float32))))
+                    del full
+                if smooth is not None:
+                    verts, self.mesh_stats["smooth"] = mesh.smooth(verts.contiguous(), faces.contiguous(), iterations=int(smooth),
+                                                                   weights=smooth_weights)
                 self.mesh_stats.pop("edge_ids", None)
                 if normals is not None:
                     verts, nrm = self._refine_mesh(network, verts, faces, res, lo, step, float(level), 0, normals, shapeCodes, expType,

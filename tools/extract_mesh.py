@@ -31,6 +31,11 @@ the extraction's.  ON SEEDED WEIGHTS THE COMPONENTS SAY NOTHING ABOUT THE FLOATE
 closed where the input is, not necessarily manifold.  What the method does to a trained face has not been measured: seeded weights say
 nothing about it.  ``--simplify-error`` measures the surface distance between the unsimplified and the simplified mesh, both ways
 (``mesh.surface_distance`` sampled at one grid step), and prints it; on seeded weights it says nothing about a trained face either.
+
+``--smooth N`` runs N iterations of Taubin smoothing over the vertices (``mesh.smooth``: lam 0.5, mu -0.53, the boundary fixed;
+``--smooth-weights uniform|cotangent``) after all of the above and before ``--normals`` and ``--colors``; the tool prints the statistics
+and the signed volume before and after (``mesh.components``; the mesh is extracted a second time without smoothing for it).  Smoothing
+moves the vertices off the level set.  On seeded weights it says nothing about a trained face.
 """
 import argparse
 import itertools
@@ -118,6 +123,30 @@ def simplify_report(st):
           f"by more than one face (non-manifold there)")
 
 
+def smooth_arg(text):
+    try:
+        n = int(text)
+    except ValueError:
+        n = 0
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"{text!r}: want an integer >= 1 (Taubin iterations)")
+    return n
+
+
+def signed_volume(verts, faces):
+    """The mesh's signed volume: the sum over its components (mesh.components)."""
+    return float(mesh.components(verts.contiguous(), faces.contiguous())["volume"].sum())
+
+
+def smooth_report(st, weights, volume_before, volume_after):
+    """The statistics of mesh.smooth (render.mesh_stats["smooth"]) and the signed volume on both sides of it."""
+    print(f"smoothed: {st['passes']} passes with {weights} weights; {st['n_pinned']} vertices pinned ({st['n_boundary']} on the boundary), "
+          f"{st['n_isolated']} without neighbours, largest degree {st['degree_max']}, {st['edges_nonmanifold']} non-manifold edges")
+    print(f"  displacement: max {st['max_displacement']:.6g}, mean {float(st['displacement'].mean()) if st['displacement'].numel() else 0.0:.6g}; "
+          f"{st['flat_corners']} flat corners, {st['negative_weights']} negative weights clamped, {st['zero_weight']} vertices kept for a zero weight sum")
+    print(f"  signed volume {volume_before:.6g} -> {volume_after:.6g} ({volume_after / volume_before if volume_before else float('nan'):.4f} x)")
+
+
 def distance_report(err, what="unsimplified -> simplified", back="simplified -> unsimplified"):
     """The statistics of mesh.surface_distance, one line per direction."""
     for d, name in (("a_to_b", what), ("b_to_a", back)):
@@ -159,7 +188,12 @@ def main(argv=None):
                     "or the cluster mean (plain clustering)")
     ap.add_argument("--simplify-error", action="store_true", help="with --simplify: measure and print the surface distance between the "
                     "unsimplified and the simplified mesh (mesh.surface_distance, sampled at one grid step)")
+    ap.add_argument("--smooth", type=smooth_arg, default=None, metavar="N", help="N iterations of Taubin smoothing (mesh.smooth) after "
+                    "--components / --refine / --simplify, before --normals / --colors")
+    ap.add_argument("--smooth-weights", choices=("uniform", "cotangent"), default="uniform", help="with --smooth: the Laplacian's weights")
     a = ap.parse_args(argv)
+    if a.compare_dense and a.smooth is not None:
+        ap.error("--compare-dense compares the unsmoothed meshes: drop --smooth")
     if a.simplify_error and a.simplify is None:
         ap.error("--simplify-error needs --simplify")
     if a.compare_dense and a.simplify is not None:
@@ -177,7 +211,7 @@ def main(argv=None):
     kw = dict(bounds=bounds, resolution=res, shapeCodes=bm, expType=20, expCodes=exp, netchunk=a.netchunk)
     out = render.extract_mesh(net, level=a.level, uvCodes=uv if a.colors else None, colors=a.colors, brick=a.brick, refine=a.refine,
                               normals=a.normals, components=a.components, simplify=a.simplify, placement=a.placement,
-                              simplify_error=a.simplify_error, **kw)
+                              simplify_error=a.simplify_error, smooth=a.smooth, smooth_weights=a.smooth_weights, **kw)
     verts, faces = out[0], out[1]
     mesh.write_ply(a.out, verts, faces, out[2] if a.colors else None, normals=out[-1] if a.normals else None)
     print(f"wrote {a.out}: V = {verts.shape[0]}, F = {faces.shape[0]}")
@@ -195,6 +229,14 @@ def main(argv=None):
             print("surface distance between the unsimplified and the simplified mesh" +
                   (" (seeded synthetic weights: NOTHING about a trained face)" if a.synthetic else "") + ":")
             distance_report(render.mesh_stats["simplify_error"])
+    if a.smooth is not None:
+        if a.synthetic:
+            print("seeded synthetic weights: the smoothing below says NOTHING about what the method does to a trained face")
+        stats = dict(render.mesh_stats)
+        before = render.extract_mesh(net, level=a.level, brick=a.brick, refine=a.refine, components=a.components, simplify=a.simplify,
+                                     placement=a.placement, **kw)
+        smooth_report(stats["smooth"], a.smooth_weights, signed_volume(before[0], before[1]), signed_volume(verts, faces))
+        render.mesh_stats = stats
     if a.normals == "density":
         print(f"density normals: {render.mesh_stats['zero_normals']} of {verts.shape[0]} vertices have a vanishing gradient")
     if a.brick is not None:

@@ -14,6 +14,9 @@ level once more with ``extract_mesh(simplify=M)`` (vertex clustering on cells of
 it from the same pose and prints its agreement with the volume next to the unsimplified mesh's, and the agreement of the simplified mesh
 with the unsimplified one (the unsimplified mesh's mask standing in as ``acc`` with ``acc_min`` 0.5): what the simplification cost in depth
 from this one camera.  Next to it the surface distance between the two meshes (``mesh.surface_distance``: all of the surface, both ways).
+``--smooth N`` does the same with ``extract_mesh(smooth=N)`` (Taubin smoothing, ``--smooth-weights uniform|cotangent``): the depth agreement
+with and without smoothing, and ``mesh.surface_distance(signed=True)`` between the two meshes — which way the surface moved, and how far
+(a mesh that is open at the box has no inside: the tool then says so instead).
 
 Networks come from a checkpoint (``--ckpt``) or seeded synthetic weights (``--synthetic DC WC DF WF``), codes from ``--fit`` or
 ``synth.codes`` — the options of tools/render_geometry.py.  ON SEEDED WEIGHTS THE AGREEMENT NUMBERS MEAN NOTHING ABOUT A TRAINED FACE:
@@ -34,7 +37,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mofanerf_amd import mesh, synth  # noqa: E402
 from mofanerf_amd.io import PngSink  # noqa: E402
 from mofanerf_amd.rays import pose_spherical  # noqa: E402
-from extract_mesh import components_arg, simplify_arg  # noqa: E402
+from extract_mesh import components_arg, simplify_arg, smooth_arg  # noqa: E402
 from render_culled import load  # noqa: E402
 
 
@@ -71,6 +74,9 @@ def main(argv=None):
                     "extract_mesh(components=...) keeps the component with the most faces, or every one with at least N faces")
     ap.add_argument("--simplify", type=simplify_arg, default=None, metavar="M", help="also extract every level simplified on cells of M grid "
                     "steps (extract_mesh(simplify=M)); its agreement with the volume and with the unsimplified mesh is printed")
+    ap.add_argument("--smooth", type=smooth_arg, default=None, metavar="N", help="also extract every level smoothed by N Taubin iterations "
+                    "(extract_mesh(smooth=N)); its agreement with the volume and the signed distance to the unsmoothed mesh are printed")
+    ap.add_argument("--smooth-weights", choices=("uniform", "cotangent"), default="uniform", help="with --smooth: the Laplacian's weights")
     ap.add_argument("--size", type=int, default=512, help="frame height = width")
     ap.add_argument("--samples", type=int, nargs=2, default=[64, 128], metavar=("N_SAMPLES", "N_IMPORTANCE"))
     ap.add_argument("--near", type=float, default=8.0)
@@ -143,6 +149,40 @@ def main(argv=None):
                 stem = os.path.join(a.out, f"level_{level:g}" + (f"_refine{k}" if k else ""))
                 sink.submit(stem + "_mesh.png", rgb)
                 sink.submit(stem + "_mesh_depth.png", (((depth - a.near) / span) * mask)[..., None].expand(H, H, 3))
+                if a.smooth is not None:
+                    # the same mesh smoothed, from the same pose: against the volume, against the unsmoothed mesh, and which way it moved
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    mv, mf = render.extract_mesh(net, bounds=bounds, resolution=tuple(a.resolution), level=level, shapeCodes=bm, expType=20,
+                                                 expCodes=exp, netchunk=a.netchunk, brick=a.brick, refine=k, components=a.components,
+                                                 smooth=a.smooth, smooth_weights=a.smooth_weights)[:2]
+                    torch.cuda.synchronize()
+                    t_smooth = (time.perf_counter() - t0) * 1e3
+                    ms = {key: val for key, val in render.mesh_stats["smooth"].items() if key != "displacement"}
+                    t_mmesh, _, (mrgb, mdepth, mmask, _) = median_ms(lambda: render.render_mesh(H, H, K, pose, mv, mf, znear=a.znear), a.warmup, a.frames)
+                    m_vol = mesh.depth_agreement(mdepth, mmask, depth_vol, acc, a.acc_min)
+                    m_full = mesh.depth_agreement(mdepth, mmask, depth, mask.to(torch.float32), 0.5)
+                    row["smoothed"] = {"smooth": a.smooth, "weights": a.smooth_weights, "extract_ms": round(t_smooth, 2), "render_mesh_ms": t_mmesh, **ms,
+                                       "against_volume": m_vol, "against_unsmoothed": m_full}
+                    print(f"  smooth={a.smooth} ({a.smooth_weights} weights): {ms['passes']} passes, {ms['n_pinned']} of {int(mv.shape[0])} vertices pinned, "
+                          f"max displacement {ms['max_displacement']:.5f}; extract + smooth {t_smooth:.1f} ms, render_mesh {t_mmesh:.3f} ms", flush=True)
+                    print(f"    against the volume:     IoU {m_vol['iou']:.4f} (unsmoothed {agree['iou']:.4f}), |depth difference| median "
+                          f"{m_vol['median_abs']:.5f} (unsmoothed {agree['median_abs']:.5f}), 95 % {m_vol['p95_abs']:.5f} (unsmoothed {agree['p95_abs']:.5f})")
+                    print(f"    against the unsmoothed mesh: IoU {m_full['iou']:.4f}, |depth difference| median {m_full['median_abs']:.5f}, "
+                          f"95 % {m_full['p95_abs']:.5f}", flush=True)
+                    try:
+                        spacing = float(min(mesh.grid_spec(bounds, tuple(a.resolution))[2]))
+                        err = mesh.surface_distance(verts.contiguous(), faces.contiguous(), mv.contiguous(), mf.contiguous(), spacing, signed=True)
+                        row["smoothed"]["surface_distance"] = {"hausdorff": err["hausdorff"], **{d: {q: err[d][q] for q in (
+                            "mean", "max", "p95", "signed_mean", "inside_fraction", "max_inside", "max_outside")} for d in ("a_to_b", "b_to_a")}}
+                        e = err["a_to_b"]
+                        print(f"    signed surface distance, unsmoothed -> smoothed (negative: the sample lies inside the smoothed mesh, which moved "
+                              f"outward there): signed mean {e['signed_mean']:.5f}, {100 * e['inside_fraction']:.1f} % inside, largest inside "
+                              f"{e['max_inside']:.5f}, outside {e['max_outside']:.5f}; unsigned mean {e['mean']:.5f}, Hausdorff {err['hausdorff']:.5f}"
+                              + ("  (seeded weights: nothing about a trained face)" if a.synthetic else ""), flush=True)
+                    except mesh.lib.MofaError as ex:                      # an open mesh has no inside (a surface that leaves the box)
+                        print(f"    signed surface distance: not available ({ex})", flush=True)
+                    sink.submit(stem + f"_smooth{a.smooth}_mesh.png", mrgb)
                 if a.simplify is None:
                     continue
                 # the same mesh simplified, from the same pose: against the volume, and against the unsimplified mesh
@@ -177,7 +217,7 @@ def main(argv=None):
                 sink.submit(stem + f"_simplify{a.simplify}_mesh.png", srgb)
     print(json.dumps({"size": H, "samples": a.samples, "angle": a.angle, "radius": a.radius, "near": a.near, "far": a.far, "acc_min": a.acc_min,
                       "median_threshold": a.median_threshold, "resolution": a.resolution, "brick": a.brick, "refine": a.refine, "components": a.components,
-                      "simplify": a.simplify, "wave_min_pixels": mesh.WAVE_MIN_PIXELS, "synthetic_weights": bool(a.synthetic),
+                      "simplify": a.simplify, "smooth": a.smooth, "wave_min_pixels": mesh.WAVE_MIN_PIXELS, "synthetic_weights": bool(a.synthetic),
                       "agreement_says_nothing_about_a_trained_face": bool(a.synthetic), "render_geometry_ms": t_vol,
                       "render_geometry_ms_all": all_vol, "levels": rows, "out": a.out}))
 
