@@ -128,6 +128,7 @@ def test_the_entry_point_keeps_sigma_everywhere_and_rgb_on_the_live_rows(W, poin
     sigma = full[..., 3]
     live = ~(sigma <= 0)
     print("entry", W, points, n, live_n)
+    # (the ragged case; a live count at an exact multiple of 256 is prescribed in tests/test_gpu_gate_patterns.py)
     assert n == R * S and live_n == int(live.sum()) and 0 < live_n < n and live_n % 256 != 0
     assert torch.isnan(sigma[3]).all() and live[3].all()
     assert torch.equal(bits(gated[..., 3]), bits(sigma))
