@@ -506,6 +506,60 @@ int mofa_wind_query(const float* points, int64_t N, const int64_t* order, const 
                     int32_t axis, const double origin[2], const double cell[2], const int32_t n[2], const int32_t* cell_start,
                     const int32_t* pair_face, int64_t P, int32_t* winding, int32_t* crossings, int64_t* counts, void* stream);
 
+/* Mesh ray casting: the first or the last hit of N rays o + t d on a triangle mesh (verts [V,3] float, faces [F,3] int32), through the grid
+ * of face lists of the surface distance above (mofa_dist_bin_count / mofa_dist_bin_emit, the caller's sort, cell_start; mesh.py drives the
+ * passes: mesh.ray_cast, mesh.ray_bounds; 1 <= N, V, F <= 2^31 - 1).  d is NOT normalised: t is the ray parameter.  No float or double
+ * atomics: the same input gives the same bytes every time; the only atomics are the integer counters counts[MOFA_RAY_COUNTS] (int64,
+ * DEVICE, zeroed by the caller; slot 0 is mofa_dist_bin_count's degenerate faces, so one buffer serves both).  The kernel checks the
+ * indices it dereferences: a bad one is skipped.  It waits on no other thread and its loops are bounded by the grid's dimensions.  All
+ * arithmetic is fp64 on the fp32 values widened, every operation rounded separately (no FMA).
+ *   the pair           ray (o, d) against (a, b, c): the watertight test of Woop, Benthin and Wald (JCGT 2013)
+ *                        kz = the axis of the largest |d| (a tie: the lowest axis), kx = (kz + 1) % 3, ky = (kz + 2) % 3, swapped when d[kz] < 0
+ *                        Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz]
+ *                        for X = a, b, c:  X' = X - o;  Xx = X'[kx] - Sx X'[kz], Xy = X'[ky] - Sy X'[kz], Xz = Sz X'[kz]   (-> A, B, C)
+ *                        U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax;  some of them < 0 and some > 0: a miss (zeros are inside)
+ *                        det = (U + V) + W;  det == 0: a miss
+ *                        t = ((U Az + V Bz) + W Cz) / det, then t = t < zlo ? zlo : t, t = t > zhi ? zhi : t with
+ *                          zlo = Az < Bz ? Az : Bz, zlo = Cz < zlo ? Cz : zlo and zhi likewise with > (t is a convex combination of the three
+ *                          depths: the clamp removes rounding only)
+ *                        point[k] = o[k] + t d[k];  bary = (U / det, V / det, W / det);  front = det > 0 (the ray runs against (b - a) x (c - a))
+ *                        the box rule:  tol = 2^-42 (((|o0| + |o1|) + |o2|) + ((m0 + m1) + m2)) with m[k] = max(|a[k]|, |b[k]|, |c[k]|);  the pair is
+ *                          a miss (counts[MOFA_RAY_OFF_BOX]) when on some axis point[k] < min(a[k], b[k], c[k]) - tol or point[k] >
+ *                          max(a[k], b[k], c[k]) + tol: the hit of a ray nearly in the face's plane, whose weights are rounding noise, counts
+ *                          only where it lies on the face's own box.  A decision of the pair alone; the walk below leans on it.
+ *                        accepted when t_min <= t <= t_max (both ends included) and cull does not exclude the side:
+ *                          MOFA_RAY_CULL_BACK drops det < 0, MOFA_RAY_CULL_FRONT drops det > 0
+ *                      The two products of an edge function are the same bits in both faces that share the edge and their differences exact
+ *                      negatives: no ray passes between two faces.  MOFA_RAY_FIRST: the smaller t wins, MOFA_RAY_LAST: the larger, among equal
+ *                      t the lower face index: the answer is a function of the mesh and the ray alone.
+ *   mofa_ray_query     one thread per ray; thread i takes ray order[i] (int64 [N], DEVICE: a permutation that puts similar rays next to each
+ *                      other; NULL = the identity) and writes its slots of t [N] (float), t64 [N] (double), face [N] (int32), front [N]
+ *                      (uint8), bary [N,3] and point [N,3] (float, rounded once from fp64).  The grid (origin, cell, slack, n, cell ids, idx) is
+ *                      the surface distance's.  With hi[k] = origin[k] + (double) n[k] cell[k], M[k] = max(|origin[k]|, |hi[k]|),
+ *                      R = ((|o0| + |o1|) + |o2|) + ((M0 + M1) + M2), s[k] = slack[k] + 2^-40 R and Wt = |Sz| s[kz], the ray visits the slabs
+ *                      j = 0 .. n[kz] - 1 of cells along kz in ray order (MOFA_RAY_LAST: in reverse); plane(j) = origin[kz] + (double) j cell[kz]:
+ *                        Sz > 0:  lo_t = (plane(j) - o[kz]) Sz - Wt,      hi_t = (plane(j + 1) - o[kz]) Sz + Wt
+ *                        Sz < 0:  lo_t = (plane(j + 1) - o[kz]) Sz - Wt,  hi_t = (plane(j) - o[kz]) Sz + Wt
+ *                      Every hit of a face listed in slab j has lo_t <= t <= hi_t for one such j, and lo_t, hi_t are monotone
+ *                      along the walk.  FIRST: the walk ends before slab j when (a hit is held and its t < lo_t, strictly: an equal t with a lower
+ *                      index may sit there) or lo_t > t_max;  LAST: when (a hit is held and its t > hi_t) or hi_t < t_min.  With
+ *                      ta = max(lo_t, t_min), tb = min(hi_t, t_max), a slab with not ta <= tb is passed over; in any other, for k = kx, ky:
+ *                        pa = o[k] + ta d[k], pb = o[k] + tb d[k];  cells idx(min(pa, pb) - s[k]) .. idx(max(pa, pb) + s[k])
+ *                      and every face listed in a cell of that rectangle of slab j is tested (a face tested twice changes nothing).
+ *                      A ray with a non-finite origin or direction or with d = 0 gets face -1, t / t64 / bary / point NaN and is counted in
+ *                      counts[MOFA_RAY_BAD]; a ray without a hit gets face -1, t and t64 +infinity, bary and point NaN.
+ *                      counts[MOFA_RAY_TESTS] += the pairs tested, counts[MOFA_RAY_OFF_BOX] += those the box rule refused,
+ *                      counts[MOFA_RAY_MAX_SLABS] = max(the slabs a ray visited): all three depend on the grid, no result bit does.
+ *                      pair_face may be NULL when P = 0.
+ * A null pointer, t_min > t_max or a NaN bound, an unknown which / cull or a grid out of range returns MOFA_EINVAL with a message. */
+enum { MOFA_RAY_DEGENERATE = 0, MOFA_RAY_BAD = 1, MOFA_RAY_TESTS = 2, MOFA_RAY_MAX_SLABS = 3, MOFA_RAY_OFF_BOX = 4, MOFA_RAY_COUNTS = 5 };
+enum { MOFA_RAY_FIRST = 0, MOFA_RAY_LAST = 1 };
+enum { MOFA_RAY_CULL_NONE = 0, MOFA_RAY_CULL_BACK = 1, MOFA_RAY_CULL_FRONT = 2 };
+int mofa_ray_query(const float* origins, const float* dirs, int64_t N, const int64_t* order, const float* verts, int64_t V,
+                   const int32_t* faces, int64_t F, const double origin[3], const double cell[3], const double slack[3], const int32_t n[3],
+                   const int32_t* cell_start, const int32_t* pair_face, int64_t P, double t_min, double t_max, int32_t which, int32_t cull,
+                   float* t, double* t64, int32_t* face, uint8_t* front, float* bary, float* point, int64_t* counts, void* stream);
+
 /* Mesh smoothing: Taubin lambda | mu filtering of the vertices of a triangle mesh (verts [V,3] float, faces [F,3] int32) over a fixed-order
  * vertex adjacency (mesh.py drives the passes: mesh.vertex_adjacency, mesh.smooth; 1 <= V, F, E <= 2^31 - 1).  No float or double atomics and
  * a fixed summation order: the same input gives the same bytes every time; the only atomics are the integer counters

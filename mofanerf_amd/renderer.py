@@ -1045,6 +1045,23 @@ class Renderer(torch.nn.Module):
             extras = {"face": out["face"], "counts": out["counts"], "normal": out["normal"]}
         return rgb, out["depth"], out["mask"], extras
 
+    def mesh_bounds(self, H, W, K, c2w, verts, faces, near, far, margin, ndc=False, grid=None):
+        """Per-ray sampling bounds that hug a mesh of the face — what :meth:`extract_mesh` returns, possibly filtered, simplified or
+        smoothed — for the camera ``K`` / ``c2w``: the rays :meth:`render_fitting` itself generates for that pose are cast against the
+        mesh (``mesh.ray_bounds``: first and last hit in ``[near, far]``, widened by ``margin``, clipped to ``[near, far]``; no network
+        runs).  Returns ``(near [H*W,1], far [H*W,1], hit [H,W] bool)``: ``render_fitting(..., near=n, far=f, ndc=False)`` and
+        :meth:`render_geometry` take the two columns as they are, and ``hit`` is the silhouette before any sample is drawn.  A ray that
+        misses the mesh keeps the scalar bounds.  ``ndc=True`` is refused: the sampler's rays are NDC rays then, and the mesh lives in
+        scene space."""
+        from . import mesh
+        if ndc:
+            raise lib.MofaError("mesh_bounds: ndc=True: the sampler's rays are NDC rays, the mesh lives in scene space (render with ndc=False)")
+        if c2w is None:
+            raise lib.MofaError("mesh_bounds: needs the camera pose c2w")
+        rays_o, rays_d, _, _ = self._make_rays(H, W, K, c2w, None, True, None, False)
+        b = mesh.ray_bounds(rays_o, rays_d, verts, faces, near, far, margin, grid=grid)
+        return b["near"].reshape(-1, 1), b["far"].reshape(-1, 1), b["hit"].reshape(int(H), int(W))
+
     def render_path_mesh(self, render_poses, hwf, K, verts, faces, colors=None, savedir=None, znear=1e-3, ambient=0.3, near=None, far=None,
                          name=None):
         """One :meth:`render_mesh` frame per pose: a turntable of an exported mesh at the cost of a z-buffer.  With ``savedir`` two 8-bit

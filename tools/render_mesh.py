@@ -17,6 +17,11 @@ from this one camera.  Next to it the surface distance between the two meshes (`
 ``--smooth N`` does the same with ``extract_mesh(smooth=N)`` (Taubin smoothing, ``--smooth-weights uniform|cotangent``): the depth agreement
 with and without smoothing, and ``mesh.surface_distance(signed=True)`` between the two meshes — which way the surface moved, and how far
 (a mesh that is open at the box has no inside: the tool then says so instead).
+``--ray-cast`` casts the frame's own ``get_rays`` rays against every mesh (``mesh.ray_cast``, first hit) and prints, against the rasterised
+frame of the same pose: the share of pixels with the same mask, the median / 95 % / largest |depth difference| on the pixels both hit, the
+share of those with the same face index, and the times of both.  ``--mesh-bounds MARGIN`` additionally renders the volume once more with
+the mesh's per-ray bounds (``Renderer.mesh_bounds``: first and last hit +- MARGIN) and prints ``mesh.depth_agreement`` of the scalar-bounds
+render and of the mesh-bounds render against the rasterised mesh, and the share of the ``[near, far]`` span the bounds remove.
 
 Networks come from a checkpoint (``--ckpt``) or seeded synthetic weights (``--synthetic DC WC DF WF``), codes from ``--fit`` or
 ``synth.codes`` — the options of tools/render_geometry.py.  ON SEEDED WEIGHTS THE AGREEMENT NUMBERS MEAN NOTHING ABOUT A TRAINED FACE:
@@ -36,7 +41,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mofanerf_amd import mesh, synth  # noqa: E402
 from mofanerf_amd.io import PngSink  # noqa: E402
-from mofanerf_amd.rays import pose_spherical  # noqa: E402
+from mofanerf_amd.rays import get_rays, pose_spherical  # noqa: E402
 from extract_mesh import components_arg, simplify_arg, smooth_arg  # noqa: E402
 from render_culled import load  # noqa: E402
 
@@ -77,6 +82,10 @@ def main(argv=None):
     ap.add_argument("--smooth", type=smooth_arg, default=None, metavar="N", help="also extract every level smoothed by N Taubin iterations "
                     "(extract_mesh(smooth=N)); its agreement with the volume and the signed distance to the unsmoothed mesh are printed")
     ap.add_argument("--smooth-weights", choices=("uniform", "cotangent"), default="uniform", help="with --smooth: the Laplacian's weights")
+    ap.add_argument("--ray-cast", action="store_true", help="also cast the frame's rays against every mesh (mesh.ray_cast) and print its agreement "
+                    "with the rasterised frame and the times of both")
+    ap.add_argument("--mesh-bounds", type=float, default=None, metavar="MARGIN", help="also render the volume with the mesh's per-ray bounds "
+                    "(Renderer.mesh_bounds, first / last hit +- MARGIN) and print both renders' agreement with the rasterised mesh")
     ap.add_argument("--size", type=int, default=512, help="frame height = width")
     ap.add_argument("--samples", type=int, nargs=2, default=[64, 128], metavar=("N_SAMPLES", "N_IMPORTANCE"))
     ap.add_argument("--near", type=float, default=8.0)
@@ -104,9 +113,9 @@ def main(argv=None):
     if a.synthetic:
         print("seeded synthetic weights: the agreement numbers below say NOTHING about a trained face (only the times carry over)", flush=True)
 
-    def volume():
+    def volume(**bounds_):
         out = render.render_geometry(H, H, K, chunk=a.chunk, c2w=pose, ndc=False, shapeCodes=bm, expType=20, expCodes=exp, median=True,
-                                     acc_min=a.acc_min, median_threshold=a.median_threshold, **kw)
+                                     acc_min=a.acc_min, median_threshold=a.median_threshold, **dict(kw, **bounds_))
         render.check_launches(block=True)
         return out
 
@@ -149,6 +158,39 @@ def main(argv=None):
                 stem = os.path.join(a.out, f"level_{level:g}" + (f"_refine{k}" if k else ""))
                 sink.submit(stem + "_mesh.png", rgb)
                 sink.submit(stem + "_mesh_depth.png", (((depth - a.near) / span) * mask)[..., None].expand(H, H, 3))
+                if a.ray_cast or a.mesh_bounds is not None:
+                    # the frame's own rays against the mesh: the rasteriser's pixels are these rays snapped to 1 / 256 pixel
+                    ro, rd = (x.reshape(-1, 3).contiguous() for x in get_rays(H, H, K, pose, device=verts.device))
+                    vc, fc = verts.contiguous(), faces.contiguous()
+                    t_cast, _, cast = median_ms(lambda: mesh.ray_cast(ro, rd, vc, fc), a.warmup, a.frames)
+                    rmask, rdepth, rface = cast["hit"].reshape(H, H), cast["t"].reshape(H, H), cast["face"].reshape(H, H)
+                    both = rmask & mask
+                    dd = (rdepth - depth)[both].abs().double()
+                    q = lambda v: float(torch.quantile(dd, v)) if dd.numel() else float("nan")
+                    row["ray_cast"] = {"ray_cast_ms": t_cast, "rasterize_ms": t_raster, "grid": list(cast["grid"]), "counts": cast["counts"],
+                                       "same_mask": float((rmask == mask).double().mean()), "n_cast": int(rmask.sum()), "n_raster": int(mask.sum()),
+                                       "n_both": int(both.sum()), "median_abs": q(0.5), "p95_abs": q(0.95),
+                                       "max_abs": float(dd.max()) if dd.numel() else float("nan"),
+                                       "same_face": float((rface[both] == mex["face"][both]).double().mean()) if dd.numel() else float("nan")}
+                    rc = row["ray_cast"]
+                    print(f"  ray_cast ({H * H} rays, grid {tuple(cast['grid'])}, {cast['counts']['face_tests'] / (H * H):.1f} face tests per ray): "
+                          f"{t_cast:.3f} ms against rasterize's {t_raster:.3f} ms; same mask on {100 * rc['same_mask']:.3f} % of the pixels (cast "
+                          f"{rc['n_cast']}, rasterised {rc['n_raster']}, both {rc['n_both']}), |depth difference| median {rc['median_abs']:.2e}, 95 % "
+                          f"{rc['p95_abs']:.2e}, max {rc['max_abs']:.2e}; the same face on {100 * rc['same_face']:.3f} % of them", flush=True)
+                    if a.mesh_bounds is not None:
+                        t_b, _, (bn, bf, bhit) = median_ms(lambda: render.mesh_bounds(H, H, K, pose, vc, fc, a.near, a.far, a.mesh_bounds), a.warmup,
+                                                           a.frames)
+                        t_bvol, _, (_, _, bacc, bex) = median_ms(lambda: volume(near=bn, far=bf), a.warmup, a.frames)
+                        scalar = mesh.depth_agreement(depth, mask, depth_vol, acc, a.acc_min)
+                        hugged = mesh.depth_agreement(depth, mask, bex["depth_median"], bacc, a.acc_min)
+                        removed = 1.0 - float(((bf - bn) / (a.far - a.near)).double().mean())
+                        row["mesh_bounds"] = {"margin": a.mesh_bounds, "mesh_bounds_ms": t_b, "render_geometry_ms": t_bvol, "rays_hit": int(bhit.sum()),
+                                              "span_removed": removed, "scalar_bounds": scalar, "mesh_bounds": hugged}
+                        print(f"  mesh_bounds (margin {a.mesh_bounds:g}): {t_b:.3f} ms, {int(bhit.sum())} of {H * H} rays hit, {100 * removed:.1f} % of the "
+                              f"[near, far] span removed; render_geometry with them {t_bvol:.2f} ms (scalar bounds {t_vol:.2f} ms)")
+                        for label, g in (("scalar bounds", scalar), ("mesh bounds  ", hugged)):
+                            print(f"    {label} against the rasterised mesh: IoU {g['iou']:.4f}, |depth difference| median {g['median_abs']:.5f}, 95 % "
+                                  f"{g['p95_abs']:.5f}", flush=True)
                 if a.smooth is not None:
                     # the same mesh smoothed, from the same pose: against the volume, against the unsmoothed mesh, and which way it moved
                     torch.cuda.synchronize()
@@ -217,7 +259,7 @@ def main(argv=None):
                 sink.submit(stem + f"_simplify{a.simplify}_mesh.png", srgb)
     print(json.dumps({"size": H, "samples": a.samples, "angle": a.angle, "radius": a.radius, "near": a.near, "far": a.far, "acc_min": a.acc_min,
                       "median_threshold": a.median_threshold, "resolution": a.resolution, "brick": a.brick, "refine": a.refine, "components": a.components,
-                      "simplify": a.simplify, "smooth": a.smooth, "wave_min_pixels": mesh.WAVE_MIN_PIXELS, "synthetic_weights": bool(a.synthetic),
+                      "simplify": a.simplify, "smooth": a.smooth, "ray_cast": a.ray_cast, "mesh_bounds": a.mesh_bounds, "wave_min_pixels": mesh.WAVE_MIN_PIXELS, "synthetic_weights": bool(a.synthetic),
                       "agreement_says_nothing_about_a_trained_face": bool(a.synthetic), "render_geometry_ms": t_vol,
                       "render_geometry_ms_all": all_vol, "levels": rows, "out": a.out}))
 
