@@ -560,6 +560,49 @@ int mofa_ray_query(const float* origins, const float* dirs, int64_t N, const int
                    const int32_t* cell_start, const int32_t* pair_face, int64_t P, double t_min, double t_max, int32_t which, int32_t cull,
                    float* t, double* t64, int32_t* face, uint8_t* front, float* bary, float* point, int64_t* counts, void* stream);
 
+/* Depth-map fusion: a truncated signed distance volume (Curless and Levoy 1996; KinectFusion) with silhouette carving on the lattice of
+ * mofa_grid_points (nx x ny x nz samples, idx = (i ny + j) nz + k, >= 2 samples per axis, nx ny nz < 2^31), integrated from depth frames
+ * whose depth is the RAY PARAMETER of get_rays (what render_geometry without NDC, mofa_raster_resolve and mofa_ray_query return), and the
+ * marchable field made from it: mofa_iso_count / mofa_iso_emit at level 0 give the surface the frames show (mesh.py drives the passes:
+ * mesh.tsdf_volume / tsdf_integrate / tsdf_field / tsdf_surface).  One thread per voxel, no atomics: the same frames in the same order give
+ * the same bytes, and the views [a | b] in two calls give the bytes of one call with a + b.  All arithmetic is fp64 on the fp32 inputs
+ * widened, every operation rounded separately (no FMA).
+ *   the state            per voxel acc (double: the weighted sum of the truncated distances), wsum (double: the sum of the weights), front
+ *                        (int32: the observations that entered acc) and behind (int32: the views in which the voxel lay behind the seen
+ *                        surface by more than trunc); four DEVICE arrays of nx ny nz elements, zeroed by the caller before the first frame.
+ *                        mofa_tsdf_state_bytes = 24 nx ny nz, or 0 for a lattice that is refused.
+ *   mofa_tsdf_integrate  depth [n_views,H,W] (float, DEVICE), weight the same shape or NULL (every weight 1; a weight must be finite and
+ *                        >= 0: the CALLER checks), cams [n_cams,16] (float, DEVICE; n_cams = 1: one camera for every view, or n_views):
+ *                        fx, fy, cx, cy, then the pose c[3][4] row-major (c2w of get_rays, ASSUMED orthonormal as in mofa_raster_project).
+ *                        For the voxel at x (the bits of mofa_grid_points) and every view in order:
+ *                          d[a] = x[a] - c[a][3];  p[a] = (d0 c[0][a] + d1 c[1][a]) + d2 c[2][a];  t = -p[2]
+ *                          not t > 0: the view does not see the voxel
+ *                          u = cx + fx (p0 / t), v = cy - fy (p1 / t);  pu = floor(u + 0.5), pv = floor(v + 0.5) (pixels are sampled at
+ *                          integer points);  unless 0 <= pu < W and 0 <= pv < H (tested on the doubles: a non-finite value fails) the
+ *                          view does not see the voxel
+ *                          D = depth[view][pv][pu]:  not D > 0 (NaN, -infinity, 0, negative): unknown, skipped
+ *                                                    D = +infinity: background; carve != 0: s = 1 (the ray's space is empty), else skipped
+ *                                                    else sdf = D - t;  sdf < -trunc: behind += 1, skipped;  s = sdf / trunc, s > 1: s = 1
+ *                          w = weight[view][pv][pu] or 1;  w == 0: skipped;  acc = acc + w s, wsum = wsum + w, front += 1
+ *   mofa_tsdf_field      field [nx,ny,nz] (float): wsum > 0: (float)(-(acc / wsum)), positive inside; otherwise by `unobserved`:
+ *                        MOFA_TSDF_UNOBSERVED_AUTO +1 if behind > 0 (only ever seen behind a surface) and -1 if never seen at all,
+ *                        _OUTSIDE -1, _INSIDE +1.  close_border != 0 then sets the outermost lattice layer to -1.  The field is finite.
+ *                        counts[MOFA_TSDF_COUNTS] (int64, DEVICE, written, not added to): the voxels with wsum > 0, those filled +1, those
+ *                        filled -1 (the three classes partition the lattice, border or not) and the voxels of the outermost layer the
+ *                        border overwrote (0 without close_border), by per-block sums in `workspace` (mofa_tsdf_workspace_bytes, DEVICE)
+ *                        and one fixed-order pass over them.
+ * A null pointer, a refused lattice, H or W < 1 or H W >= 2^31, n_views < 1, n_cams other than 1 or n_views, a trunc that is not finite and
+ * positive or an unknown `unobserved` returns MOFA_EINVAL with a message. */
+enum { MOFA_TSDF_OBSERVED = 0, MOFA_TSDF_FILLED_INSIDE = 1, MOFA_TSDF_FILLED_OUTSIDE = 2, MOFA_TSDF_BORDER = 3, MOFA_TSDF_COUNTS = 4 };
+enum { MOFA_TSDF_UNOBSERVED_AUTO = 0, MOFA_TSDF_UNOBSERVED_OUTSIDE = 1, MOFA_TSDF_UNOBSERVED_INSIDE = 2 };
+size_t mofa_tsdf_state_bytes(int64_t nx, int64_t ny, int64_t nz);
+size_t mofa_tsdf_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+int mofa_tsdf_integrate(int64_t nx, int64_t ny, int64_t nz, const float lo[3], const float step[3], double trunc, const float* depth,
+                        const float* weight, int64_t n_views, int32_t H, int32_t W, const float* cams, int64_t n_cams, int32_t carve, double* acc,
+                        double* wsum, int32_t* front, int32_t* behind, void* stream);
+int mofa_tsdf_field(int64_t nx, int64_t ny, int64_t nz, const double* acc, const double* wsum, const int32_t* behind, int32_t unobserved,
+                    int32_t close_border, float* field, void* workspace, int64_t* counts, void* stream);
+
 /* Mesh smoothing: Taubin lambda | mu filtering of the vertices of a triangle mesh (verts [V,3] float, faces [F,3] int32) over a fixed-order
  * vertex adjacency (mesh.py drives the passes: mesh.vertex_adjacency, mesh.smooth; 1 <= V, F, E <= 2^31 - 1).  No float or double atomics and
  * a fixed summation order: the same input gives the same bytes every time; the only atomics are the integer counters

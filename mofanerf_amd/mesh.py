@@ -9,6 +9,8 @@ density normals (``refine_vertices``, ``density_normals``, ``mofa_edge_*`` / ``m
 ``sample_faces`` samples a surface deterministically and ``surface_distance`` measures one mesh against another (``mofa_dist_*``).
 ``winding_number`` says which side of a closed mesh a point is on (``mofa_wind_*``); ``signed_distance`` and ``inside_grid`` sit on it.
 ``vertex_adjacency`` lists every vertex's neighbours in a fixed order and ``smooth`` filters the vertices over it (Taubin, ``mofa_smooth_*``).
+``tsdf_volume`` / ``tsdf_integrate`` / ``tsdf_field`` / ``tsdf_surface`` fuse depth frames (``depth_frame``) into a truncated signed distance
+volume and march its zero level: a mesh with no density level to choose (``mofa_tsdf_*``).
 
 ``Renderer.query_density`` and ``Renderer.extract_mesh`` are the user-facing entry points; this module holds the pieces they share.
 The mesh is watertight and consistently oriented (normals toward lower density); vertices and faces come out in a fixed order with
@@ -1460,8 +1462,187 @@ def ray_bounds(origins: torch.Tensor, dirs: torch.Tensor, verts: torch.Tensor, f
     return out
 
 
+_TSDF_COUNTS = ("observed", "filled_inside", "filled_outside", "border")       # MOFA_TSDF_* of the header
+_TSDF_UNOBSERVED = {"auto": 0, "outside": 1, "inside": 2}                      # MOFA_TSDF_UNOBSERVED_*
+_TSDF_STATE = (("acc", torch.float64), ("wsum", torch.float64), ("front", torch.int32), ("behind", torch.int32))
+
+
+def _tsdf_trunc(who, trunc) -> float:
+    trunc = float(trunc)
+    if not (np.isfinite(trunc) and trunc > 0):
+        raise lib.MofaError(f"{who}: trunc = {trunc} (want finite and > 0)")
+    return trunc
+
+
+def tsdf_volume(resolution, lo, step, trunc, device="cuda") -> dict:
+    """An empty truncated-signed-distance volume on the lattice of :func:`grid_points` (``resolution``, ``lo``, ``step`` as
+    :func:`grid_spec` returns them): the state :func:`tsdf_integrate` updates frame by frame.  A dict of four zeroed GPU tensors of
+    ``nx ny nz`` elements — ``acc`` (float64, the weighted sum of the truncated distances), ``wsum`` (float64, the sum of the weights),
+    ``front`` (int32, the observations that entered ``acc``), ``behind`` (int32, the views in which the voxel lay behind the seen surface by
+    more than ``trunc``) — plus ``resolution``, ``lo``, ``step``, ``trunc`` and ``frames`` (the frames integrated so far).  ``trunc``, the
+    truncation distance in scene units, is fixed for the life of the volume.  24 bytes per voxel; refused for fewer than 2 samples on an
+    axis, ``nx ny nz >= 2^31``, a ``trunc`` that is not finite and positive, or a device that is no GPU."""
+    who = "tsdf_volume"
+    res = tuple(int(n) for n in resolution)
+    if len(res) != 3:
+        raise lib.MofaError(f"{who}: resolution {resolution}: want three axes")
+    lo32, step32 = (np.asarray(v, dtype=np.float32).reshape(3).copy() for v in (lo, step))
+    if not (np.isfinite(lo32).all() and np.isfinite(step32).all() and (step32 > 0).all()):
+        raise lib.MofaError(f"{who}: lo = {lo}, step = {step} (want finite values and step > 0)")
+    trunc = _tsdf_trunc(who, trunc)
+    if max(abs(n) for n in res) > INT32_MAX or lib.load().mofa_tsdf_state_bytes(*res) == 0:
+        raise lib.MofaError(f"{who}: lattice {res[0]} x {res[1]} x {res[2]} is refused (>= 2 samples per axis, nx ny nz < 2^31)")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise lib.MofaError(f"{who}: the HIP path needs a GPU (got device {dev}); there is no CPU fallback")
+    n = res[0] * res[1] * res[2]
+    state = {name: torch.zeros(n, dtype=dtype, device=dev) for name, dtype in _TSDF_STATE}
+    state.update(resolution=res, lo=lo32, step=step32, trunc=trunc, frames=0)
+    return state
+
+
+def _tsdf_state(who, state):
+    """(resolution, device) of a volume, its tensors checked."""
+    if not isinstance(state, dict) or any(k not in state for k in ("acc", "wsum", "front", "behind", "resolution", "lo", "step", "trunc")):
+        raise lib.MofaError(f"{who}: want the state dict of tsdf_volume")
+    res = state["resolution"]
+    n = res[0] * res[1] * res[2]
+    dev = state["acc"].device
+    for name, dtype in _TSDF_STATE:
+        t = state[name]
+        if not t.is_cuda:
+            raise lib.MofaError(f"the HIP path needs tensors on the GPU (got a CPU tensor as the volume's {name}); there is no CPU fallback")
+        if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != (n,) or t.device != dev:
+            raise lib.MofaError(f"{who}: the volume's {name} is {t.dtype} {tuple(t.shape)} on {t.device} (want contiguous {dtype} [{n}] on {dev})")
+    return res, dev
+
+
+def _tsdf_cameras(who, K, c2w, n_views):
+    """float32 [n_cams,16] on the host: fx, fy, cx, cy and the 3 x 4 pose of one camera, or of one per frame."""
+    host = lambda v: np.asarray(v.detach().cpu() if torch.is_tensor(v) else v)
+    Ks, poses = host(K).astype(np.float64), host(c2w).astype(np.float32)
+    Ks, poses = (Ks[None] if Ks.ndim == 2 else Ks), (poses[None] if poses.ndim == 2 else poses)
+    if Ks.ndim != 3 or Ks.shape[1] < 2 or Ks.shape[2] < 3 or poses.ndim != 3 or poses.shape[1] < 3 or poses.shape[2] != 4:
+        raise lib.MofaError(f"{who}: K {tuple(Ks.shape)}, c2w {tuple(poses.shape)} (want [3,3] and [3,4] / [4,4], or one of each per frame)")
+    if len(Ks) not in (1, n_views) or len(poses) not in (1, n_views):
+        raise lib.MofaError(f"{who}: {len(Ks)} intrinsics and {len(poses)} poses for {n_views} frames (want one, or one per frame)")
+    n_cams = max(len(Ks), len(poses))
+    cams = np.empty((n_cams, 16), dtype=np.float32)
+    for v in range(n_cams):
+        k, p = Ks[v % len(Ks)], poses[v % len(poses)]
+        cams[v, :4] = (k[0, 0], k[1, 1], k[0, 2], k[1, 2])
+        cams[v, 4:] = p[:3, :4].reshape(-1)
+    if not np.isfinite(cams).all():
+        raise lib.MofaError(f"{who}: the cameras hold non-finite values")
+    return cams
+
+
+def depth_frame(depth: torch.Tensor, mask: torch.Tensor, background: str = "empty") -> torch.Tensor:
+    """A depth frame in the encoding :func:`tsdf_integrate` reads: ``depth`` (float32, any shape, the ray parameter of ``get_rays``) where
+    ``mask`` (bool, the same shape) holds, and elsewhere ``+inf`` for ``background="empty"`` — nothing lies on that ray: the space along it
+    is carved — or NaN for ``"unknown"`` — the pixel says nothing.  :func:`rasterize` marks its misses with depth 0, :func:`ray_cast`
+    with ``t`` = +inf (NaN for a bad ray) and a renderer with a low ``acc``: all of them go through here with their mask.  A depth <= 0
+    or NaN inside the mask stays and reads as unknown."""
+    if not torch.is_tensor(depth) or not depth.is_cuda:
+        raise lib.MofaError("the HIP path needs tensors on the GPU (got a CPU depth); there is no CPU fallback")
+    if depth.dtype != torch.float32:
+        raise lib.MofaError(f"depth_frame: want a float32 depth, got {depth.dtype}")
+    if background not in ("empty", "unknown"):
+        raise lib.MofaError(f"depth_frame: background = {background!r} (want 'empty' or 'unknown')")
+    if not torch.is_tensor(mask) or not mask.is_cuda:
+        raise lib.MofaError("the HIP path needs tensors on the GPU (got a CPU mask); there is no CPU fallback")
+    if mask.dtype != torch.bool or mask.shape != depth.shape or mask.device != depth.device:
+        raise lib.MofaError(f"depth_frame: depth {tuple(depth.shape)} on {depth.device}, mask {mask.dtype} {tuple(mask.shape)} on {mask.device} "
+                            "(want a bool mask of the depth's shape on its device)")
+    fill = float("inf") if background == "empty" else float("nan")
+    return torch.where(mask, depth.detach(), torch.full((), fill, dtype=torch.float32, device=depth.device)).contiguous()
+
+
+def tsdf_integrate(state: dict, depth: torch.Tensor, K, c2w, weight: Optional[torch.Tensor] = None, carve: bool = True, trunc=None) -> dict:
+    """Integrate depth frames into a volume of :func:`tsdf_volume` (``mofa_tsdf_integrate``; Curless and Levoy's weighted running
+    average of truncated signed distances, with silhouette carving).  ``depth`` is ``[n,H,W]`` or ``[H,W]`` float32 on the volume's device,
+    in the encoding of :func:`depth_frame`: a finite positive value is the RAY PARAMETER of the pixel's ``get_rays`` ray at the surface —
+    what ``Renderer.render_geometry`` (non-NDC), :func:`rasterize` and :func:`ray_cast` return —, ``+inf`` is background, and NaN, ``-inf``
+    and values <= 0 are unknown.  ``K`` / ``c2w`` are one camera (``[3,3]``, ``[3,4]`` or ``[4,4]``) or one per frame; the pose is assumed
+    orthonormal.  ``weight`` (the depth's shape, finite and >= 0; ``None``: 1) weighs every pixel's observation, and a zero switches it off.
+
+    Per voxel and view, in the order of the frames and in fp64 (include/mofanerf_hip.h has every operation): the voxel is taken into the
+    camera, ``t`` = its ray parameter, and the nearest pixel ``(floor(u + 0.5), floor(v + 0.5))`` is read; behind the camera or out of the
+    frame the view says nothing.  With ``D`` the pixel's depth: ``sdf = D - t``; ``sdf < -trunc`` only counts the view in ``behind``;
+    otherwise ``s = min(sdf / trunc, 1)`` is observed with the pixel's weight.  A background pixel observes ``s = 1`` when ``carve`` (the
+    whole ray is empty) and nothing otherwise.  No atomics and a fixed order: the same frames give the same bytes, and frames streamed in
+    several calls give the bytes of one call with all of them — nothing needs to hold all frames at once.  Returns ``state`` (updated in
+    place; ``state["frames"]`` counts the frames).
+
+    Raises ``MofaError`` for CPU tensors, wrong dtypes or shapes, a frame or a weight map on another device than the volume, camera counts
+    that match neither 1 nor ``n``, a weight that is negative or not finite, ``H W >= 2^31`` and a ``trunc`` that differs from the
+    volume's (it is fixed when the volume is made; ``None``: the volume's)."""
+    who = "tsdf_integrate"
+    res, dev = _tsdf_state(who, state)
+    if trunc is not None and _tsdf_trunc(who, trunc) != state["trunc"]:
+        raise lib.MofaError(f"{who}: trunc = {float(trunc)}, the volume was made with trunc = {state['trunc']} (it is fixed for the life of a volume)")
+    lib.ptr(depth)
+    if depth.dim() not in (2, 3):
+        raise lib.MofaError(f"{who}: want depth [n,H,W] or [H,W], got {tuple(depth.shape)}")
+    if depth.device != dev:
+        raise lib.MofaError(f"{who}: the volume is on {dev}, the frames on {depth.device}")
+    frames = depth.detach().reshape((-1,) + tuple(depth.shape[-2:]))
+    n, H, W = (int(v) for v in frames.shape)
+    if n < 1 or H < 1 or W < 1 or H * W > INT32_MAX:
+        raise lib.MofaError(f"{who}: {n} frames of H = {H}, W = {W} are refused (n, H, W >= 1, H W < 2^31)")
+    if weight is not None:
+        lib.ptr(weight)
+        if weight.device != dev or tuple(weight.shape) not in (tuple(depth.shape), (n, H, W)):
+            raise lib.MofaError(f"{who}: weight {tuple(weight.shape)} on {weight.device} (want the depth's {tuple(depth.shape)} on {dev})")
+        weight = weight.detach().reshape(n, H, W)
+    cams = _tsdf_cameras(who, K, c2w, n)
+    with torch.cuda.device(dev):
+        if weight is not None and not bool((torch.isfinite(weight) & (weight >= 0)).all()):
+            raise lib.MofaError(f"{who}: the weight map holds negative or non-finite values")
+        table = torch.from_numpy(cams).to(dev)
+        lib.check(lib.load().mofa_tsdf_integrate(*res, _f3(state["lo"]), _f3(state["step"]), state["trunc"], lib.ptr(frames), lib.ptr(weight), n, H, W,
+                                                 lib.ptr(table), int(cams.shape[0]), int(bool(carve)), state["acc"].data_ptr(),
+                                                 state["wsum"].data_ptr(), state["front"].data_ptr(), state["behind"].data_ptr(), lib.stream()),
+                  "mofa_tsdf_integrate")
+    state["frames"] = int(state.get("frames", 0)) + n
+    return state
+
+
+def tsdf_field(state: dict, unobserved: str = "auto", close_border: bool = True):
+    """The marchable field of a volume (``mofa_tsdf_field``): ``(field [nx,ny,nz] float32, stats)``.  ``field = -(acc / wsum)`` where a
+    voxel was observed — positive inside, ``{field >= 0}`` is the solid, the zero level the surface the frames show — and elsewhere by
+    ``unobserved``: ``"auto"`` fills ``+1`` (inside) where the voxel was only ever seen behind a surface (``behind > 0``) and ``-1`` where
+    no view saw it at all, ``"outside"`` fills ``-1`` and ``"inside"`` ``+1``.  ``close_border=True`` then sets the outermost lattice layer
+    to ``-1``, so the mesh is closed where the solid reaches the volume's edge (a frontal-only capture of a head).  The field is finite,
+    as :func:`iso_surface` demands.  ``stats``: ``observed``, ``filled_inside``, ``filled_outside`` (the three classes partition the
+    lattice), ``border`` (the voxels the border overwrote), ``voxels`` and ``frames``; reading them is the call's one host read."""
+    who = "tsdf_field"
+    res, dev = _tsdf_state(who, state)
+    if unobserved not in _TSDF_UNOBSERVED:
+        raise lib.MofaError(f"{who}: unobserved = {unobserved!r} (want 'auto', 'outside' or 'inside')")
+    L = lib.load()
+    with torch.cuda.device(dev):
+        field = torch.empty(res, dtype=torch.float32, device=dev)
+        ws = torch.empty(L.mofa_tsdf_workspace_bytes(*res), dtype=torch.uint8, device=dev)
+        counts = torch.empty(len(_TSDF_COUNTS), dtype=torch.int64, device=dev)
+        lib.check(L.mofa_tsdf_field(*res, state["acc"].data_ptr(), state["wsum"].data_ptr(), state["behind"].data_ptr(), _TSDF_UNOBSERVED[unobserved],
+                                    int(bool(close_border)), lib.ptr(field), ws.data_ptr(), counts.data_ptr(), lib.stream()), "mofa_tsdf_field")
+        stats = dict(zip(_TSDF_COUNTS, (int(v) for v in counts.cpu())))
+    stats.update(voxels=res[0] * res[1] * res[2], frames=int(state.get("frames", 0)))
+    return field, stats
+
+
+def tsdf_surface(state: dict, unobserved: str = "auto", close_border: bool = True):
+    """``(verts [V,3] float32, faces [F,3] int32)``: :func:`iso_surface` of :func:`tsdf_field` at level 0 — the surface the integrated
+    frames show, with no density level to choose.  Watertight and consistently oriented like every extraction, normals toward the
+    outside: :func:`components`, :func:`simplify`, :func:`smooth`, :func:`surface_distance`, :func:`winding_number` and
+    :func:`ray_cast` take it as it is."""
+    field, _ = tsdf_field(state, unobserved, close_border)
+    return iso_surface(field, 0.0, state["lo"], state["step"])
+
+
 SMOOTH_MAX_ITERATIONS = 1000
-_SMOOTH_COUNTS = ("flat_corners", "negative_weights", "zero_weight", "bad_index")       # MOFA_SMOOTH_* of the header
+_SMOOTH_COUNTS =("flat_corners", "negative_weights", "zero_weight", "bad_index")       # MOFA_SMOOTH_* of the header
 _SMOOTH_WEIGHTS = ("uniform", "cotangent")
 _SMOOTH_BOUNDARIES = ("fixed", "free")
 

@@ -15,6 +15,7 @@ There is no eager/CPU fallback: CPU tensors or a missing library raise ``MofaErr
 from __future__ import annotations
 
 import os
+import time
 from typing import Dict
 
 import numpy as np
@@ -1061,6 +1062,81 @@ class Renderer(torch.nn.Module):
         rays_o, rays_d, _, _ = self._make_rays(H, W, K, c2w, None, True, None, False)
         b = mesh.ray_bounds(rays_o, rays_d, verts, faces, near, far, margin, grid=grid)
         return b["near"].reshape(-1, 1), b["far"].reshape(-1, 1), b["hit"].reshape(int(H), int(W))
+
+    def fuse_geometry(self, render_poses, H, W, K, *, bounds, resolution, trunc, shapeCodes, expType=20, expCodes=None, surface="median",
+                      acc_min=0.5, background="empty", weight=None, unobserved="auto", close_border=True, **render_kwargs):
+        """A mesh of the face with NO density level: one :meth:`render_geometry` frame per pose of ``render_poses`` is fused into a
+        truncated signed distance volume over ``bounds`` / ``resolution`` (``mesh.tsdf_volume`` / ``tsdf_integrate``, truncation ``trunc``
+        in scene units) and the volume's zero level is marched (``mesh.tsdf_surface``) — the surface the renderer itself shows from
+        those poses.  Returns ``(verts [V,3] float32, faces [F,3] int32, stats)``; the mesh is what :meth:`extract_mesh` returns in kind,
+        so ``mesh.components``, ``simplify``, ``smooth``, ``surface_distance`` and the rest take it as it is.
+
+        Per frame: the depth is ``depth_median`` (``surface="median"``) or the expected depth (``"expected"``), the mask
+        ``acc >= acc_min``; ``mesh.depth_frame`` encodes the pixels outside the mask as empty space (``background="empty"``: their rays
+        carve the volume) or as unknown (``"unknown"``), and the frame is integrated as soon as it is rendered — no list of frames is
+        kept.  ``weight="acc"`` weighs a pixel's observation by ``acc`` inside the mask and by ``1 - acc`` outside it (clamped at 0);
+        ``None`` weighs every pixel 1.  ``unobserved`` / ``close_border`` are ``mesh.tsdf_field``'s.  ``render_kwargs`` go to
+        :meth:`render_geometry` (``near``, ``far``, ``occupancy``, ``chunk``, ``median_threshold`` and the ``render_kwargs_test``
+        dictionary); ``ndc=True`` is refused as in :meth:`mesh_bounds`: the depth would be an NDC depth, the volume lives in scene space.
+
+        ``stats``: the field's counters (``observed``, ``filled_inside``, ``filled_outside``, ``border``, ``voxels``, ``frames``),
+        ``hit_share`` (per frame, the share of pixels inside the mask), ``trunc``, ``resolution`` and ``times`` (seconds spent rendering,
+        integrating and marching, each phase waited for).  ``self.fuse_state`` keeps the volume.  Which ``trunc`` and ``acc_min`` suit a
+        trained face has not been measured."""
+        from . import mesh
+        who = "fuse_geometry"
+        if render_kwargs.pop("ndc", False):
+            raise lib.MofaError(f"{who}: ndc=True: the rendered depth is an NDC depth, the volume lives in scene space (render with ndc=False)")
+        if surface not in ("median", "expected"):
+            raise lib.MofaError(f"{who}: surface = {surface!r} (want 'median' or 'expected')")
+        if background not in ("empty", "unknown"):
+            raise lib.MofaError(f"{who}: background = {background!r} (want 'empty' or 'unknown')")
+        if weight not in (None, "acc"):
+            raise lib.MofaError(f"{who}: weight = {weight!r} (want None or 'acc')")
+        if unobserved not in ("auto", "outside", "inside"):
+            raise lib.MofaError(f"{who}: unobserved = {unobserved!r} (want 'auto', 'outside' or 'inside')")
+        if not np.isfinite(_scalar(acc_min)):
+            raise lib.MofaError(f"{who}: acc_min = {_scalar(acc_min)} (want a finite value)")
+        trunc = float(trunc)
+        if not (np.isfinite(trunc) and trunc > 0):
+            raise lib.MofaError(f"{who}: trunc = {trunc} (want finite and > 0)")
+        res, lo, step = mesh.grid_spec(bounds, resolution)
+        poses = [p for p in render_poses]
+        if not poses:
+            raise lib.MofaError(f"{who}: no poses")
+        H, W = int(H), int(W)
+        state, shares = None, []
+        times = {"render": 0.0, "integrate": 0.0, "march": 0.0}
+        with torch.no_grad():
+            for pose in poses:
+                t0 = time.perf_counter()
+                depth, _, acc, extras = self.render_geometry(H, W, K, c2w=pose, ndc=False, shapeCodes=shapeCodes, expType=expType, expCodes=expCodes,
+                                                             median=surface == "median", **render_kwargs)
+                if surface == "median":
+                    depth = extras["depth_median"]
+                depth, acc = depth.reshape(H, W), acc.reshape(H, W)
+                torch.cuda.synchronize(depth.device)
+                t1 = time.perf_counter()
+                if state is None:
+                    state = mesh.tsdf_volume(res, lo, step, trunc, depth.device)
+                mask = acc >= float(acc_min)
+                frame = mesh.depth_frame(depth.contiguous(), mask, background)
+                w = torch.clamp(torch.where(mask, acc, 1.0 - acc), min=0.0).contiguous() if weight == "acc" else None
+                mesh.tsdf_integrate(state, frame, K, pose, weight=w, carve=True)
+                shares.append(mask.float().mean())
+                torch.cuda.synchronize(depth.device)
+                t2 = time.perf_counter()
+                times["render"] += t1 - t0
+                times["integrate"] += t2 - t1
+            t0 = time.perf_counter()
+            field, stats = mesh.tsdf_field(state, unobserved, close_border)
+            verts, faces = mesh.iso_surface(field, 0.0, lo, step)
+            torch.cuda.synchronize(field.device)
+            times["march"] = time.perf_counter() - t0
+        stats.update(hit_share=[float(s) for s in torch.stack(shares).cpu()], trunc=trunc, resolution=res, times=times)
+        self.fuse_state = state
+        self.check_launches(block=True)
+        return verts, faces, stats
 
     def render_path_mesh(self, render_poses, hwf, K, verts, faces, colors=None, savedir=None, znear=1e-3, ambient=0.3, near=None, far=None,
                          name=None):
