@@ -638,6 +638,56 @@ int mofa_smooth_edge_weights(const double* cots, int64_t F, const int64_t* perm,
 int mofa_smooth_step(const float* verts_in, int64_t V, const int64_t* offsets, const int32_t* nbr, int64_t E, const double* weights,
                      const uint8_t* pinned, double factor, float* verts_out, int64_t* counts, void* stream);
 
+/* Mesh registration: the estimation step of rigid / similarity ICP (mesh.py drives the loop: mesh.register, mesh.fit_transform; the
+ * correspondences come from mofa_dist_query; 1 <= N, V, F <= 2^31 - 1).  No atomics of any kind and a fixed summation order that does not
+ * depend on the launch geometry: the same input gives the same bytes every time.  Every kernel checks the indices it dereferences; a
+ * correspondence with a bad one counts as rejected.  No kernel waits on another thread.  All arithmetic is fp64 on the fp32 inputs widened,
+ * every operation rounded separately (no FMA).
+ *   mofa_icp_apply    transform = [s, R (row-major 3 x 3), t] (13 doubles, HOST);  out [N,3] (float):
+ *                       out[i][r] = (float)(s * ((R[r][0] * x0 + R[r][1] * x1) + R[r][2] * x2) + t[r])
+ *   mofa_icp_terms    terms [N,36] (double).  Correspondence i has the moved point y = moved[i], the target point c = target[i], the weight
+ *                     w = weight[i] (double) and, for the plane metric, the unit normal n: with `face` ([N] int32; normals NULL) the normal of
+ *                     the closest face, ab = b - a, ac = c - a of faces[face[i]] on verts,
+ *                       cr = (ab_y ac_z - ab_z ac_y, ab_z ac_x - ab_x ac_z, ab_x ac_y - ab_y ac_x);  n = cr / sqrt((cr_x cr_x + cr_y cr_y) + cr_z cr_z)
+ *                     and with `normals` ([N,3] float; face NULL) that row, as it is.  With yh = y - pivot and d = y - c, the unknowns
+ *                     x = (omega_1..3, tau_1..3, sigma) — a small rotation about the pivot, a translation, a relative scale — see the rows
+ *                       MOFA_ICP_POINT:  J0 = [0, yh_z, -yh_y, 1, 0, 0, yh_x],  J1 = [-yh_z, 0, yh_x, 0, 1, 0, yh_y],
+ *                                        J2 = [yh_y, -yh_x, 0, 0, 0, 1, yh_z]  (that is [-[yh]x | I | yh]),  r = d
+ *                                        A_ab = w * ((J0a * J0b + J1a * J1b) + J2a * J2b),  g_a = w * ((J0a * r0 + J1a * r1) + J2a * r2),
+ *                                        e = w * ((r0 * r0 + r1 * r1) + r2 * r2)
+ *                       MOFA_ICP_PLANE:  J = [yh_y n_z - yh_z n_y, yh_z n_x - yh_x n_z, yh_x n_y - yh_y n_x, n_x, n_y, n_z,
+ *                                             (n_x * yh_x + n_y * yh_y) + n_z * yh_z]  (that is [yh x n | n | n . yh]),
+ *                                        r = (n_x * d_x + n_y * d_y) + n_z * d_z;  A_ab = w * (Ja * Jb),  g_a = w * (Ja * r),  e = w * (r * r)
+ *                     terms[i] = A's upper triangle row by row (A_00 .. A_06, A_11 .. A_66: 28 numbers), g_0 .. g_6, e.  A correspondence
+ *                     is rejected — 36 exact +0.0 — when `w > 0` is false, or a face / vertex index lies outside the mesh.  The step solves
+ *                     (sum A) x = -(sum g).  The point metric ignores face / normals / the mesh.
+ *   mofa_icp_reduce   out [ceil(M / MOFA_ICP_CHUNK), ncols] (double) from in [M, ncols], 1 <= ncols <= 36: chunk k holds the rows
+ *                     [1024 k, min(1024 (k + 1), M)); thread t of its 256 starts at 0.0 and adds the chunk's rows t, t + 256, t + 512,
+ *                     t + 768 (those below M) in that order; then `for w = 128, 64, .. 1: p[t] += p[t + w] for t < w` over the 256 partial
+ *                     sums, and p[0] is the chunk's row.  The caller reduces the chunk rows the same way until one row is left.  in != out.
+ *   mofa_icp_terms_reduce   partial [ceil(N / MOFA_ICP_CHUNK), 36]: mofa_icp_reduce of mofa_icp_terms' matrix without that matrix reaching
+ *                     memory — the same additions in the same order (a rejected row adds its zeros), the same bits.
+ *   mofa_icp_reject   rejected [N] (uint8): the border rule on what mofa_dist_query returned.  face_border [F] (uint8): bit k set when the
+ *                     edge opposite corner k of the face is a border edge (one use over both directions); vert_border [V] (uint8): the
+ *                     vertex lies on a border edge.  With z_k = (bary[i][k] == 0.0f), exactly, f = face[i]:
+ *                       rejected = any k: z_k and bit k of face_border[f];  or two of the z_k hold and vert_border[faces[f][the third k]]
+ *                     face[i] outside [0, F): 0 (no correspondence: the caller's rule, not this one).
+ * A null pointer, a count out of range, an unknown metric, a non-finite pivot, or the plane metric with both or neither of face / normals
+ * returns MOFA_EINVAL with a message. */
+#define MOFA_ICP_TERMS 36
+#define MOFA_ICP_CHUNK 1024
+enum { MOFA_ICP_POINT = 0, MOFA_ICP_PLANE = 1 };
+int mofa_icp_apply(const float* points, int64_t N, const double transform[13], float* out, void* stream);
+int mofa_icp_terms(const float* moved, const float* target, const float* normals, const int32_t* face, const float* verts, int64_t V,
+                   const int32_t* faces, int64_t F, const double* weight, int64_t N, const double pivot[3], int32_t metric, double* terms,
+                   void* stream);
+int mofa_icp_terms_reduce(const float* moved, const float* target, const float* normals, const int32_t* face, const float* verts, int64_t V,
+                          const int32_t* faces, int64_t F, const double* weight, int64_t N, const double pivot[3], int32_t metric,
+                          double* partial, void* stream);
+int mofa_icp_reduce(const double* in, int64_t M, int32_t ncols, double* out, void* stream);
+int mofa_icp_reject(const int32_t* face, const float* bary, int64_t N, const int32_t* faces, int64_t F, int64_t V, const uint8_t* face_border,
+                    const uint8_t* vert_border, uint8_t* rejected, void* stream);
+
 /* ---- occupancy-culled rendering: skip the network where an occupancy grid says the space is empty ---------------------------------
  * The grid lives on the lattice of mofa_grid_points (nx x ny x nz samples at lo + (i,j,k) step): (nx-1)(ny-1)(nz-1) cells, one byte
  * each (0 / 1), cell index (i (ny-1) + j) (nz-1) + k.  The lattice needs 2 <= n < 2^24 per axis and fewer than 2^31 cells.

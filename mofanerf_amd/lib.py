@@ -113,6 +113,11 @@ SIGNATURES = {
     "mofa_smooth_corner_cots": (C.c_int, [_fp, _fp, _i64, _i64, _fp, _fp, _fp]),
     "mofa_smooth_edge_weights": (C.c_int, [_fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp]),
     "mofa_smooth_step": (C.c_int, [_fp, _i64, _fp, _fp, _i64, _fp, _fp, C.c_double, _fp, _fp, _fp]),
+    "mofa_icp_apply": (C.c_int, [_fp, _i64, _d3, _fp, _fp]),
+    "mofa_icp_terms": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i64, _fp, _i64, _fp, _i64, _d3, _i32, _fp, _fp]),
+    "mofa_icp_terms_reduce": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i64, _fp, _i64, _fp, _i64, _d3, _i32, _fp, _fp]),
+    "mofa_icp_reduce": (C.c_int, [_fp, _i64, _i32, _fp, _fp]),
+    "mofa_icp_reject": (C.c_int, [_fp, _fp, _i64, _fp, _i64, _i64, _fp, _fp, _fp, _fp]),
     "mofa_occ_workspace_bytes": (_sz, [_i64]),
     "mofa_occ_cells": (C.c_int, [_fp, _i64, _i64, _i64, C.c_float, _i32, _fp, _fp]),
     "mofa_occ_dilate": (C.c_int, [_fp, _i64, _i64, _i64, _i32, _fp, _fp, _fp]),

@@ -11,6 +11,8 @@ density normals (``refine_vertices``, ``density_normals``, ``mofa_edge_*`` / ``m
 ``vertex_adjacency`` lists every vertex's neighbours in a fixed order and ``smooth`` filters the vertices over it (Taubin, ``mofa_smooth_*``).
 ``tsdf_volume`` / ``tsdf_integrate`` / ``tsdf_field`` / ``tsdf_surface`` fuse depth frames (``depth_frame``) into a truncated signed distance
 volume and march its zero level: a mesh with no density level to choose (``mofa_tsdf_*``).
+``register`` / ``register_meshes`` bring points or a mesh into another mesh's frame by rigid or similarity ICP over ``closest_points``' grid,
+``fit_transform`` does it for explicit correspondences and ``transform_points`` applies the result (``mofa_icp_*``).
 
 ``Renderer.query_density`` and ``Renderer.extract_mesh`` are the user-facing entry points; this module holds the pieces they share.
 The mesh is watertight and consistently oriented (normals toward lower density); vertices and faces come out in a fixed order with
@@ -19,6 +21,7 @@ no atomics, so the same grid gives the same bytes every time.  CPU tensors raise
 from __future__ import annotations
 
 import ctypes as C
+import math
 import time
 from typing import Optional, Sequence, Tuple
 
@@ -822,16 +825,8 @@ def closest_points(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tenso
     V, F, dev = _mesh_tensors(who, verts, faces)
     N = _query_points(who, points, dev)
     maxd = _max_distance(who, max_distance)
-    if grid is not None:
-        g = np.asarray(grid).reshape(-1)
-        if g.size not in (1, 3) or g.dtype.kind not in "iu" or (g < 1).any() or (g > DIST_GRID_CAP).any():
-            raise lib.MofaError(f"{who}: grid = {grid!r} (want None, an integer or three, 1 .. {DIST_GRID_CAP} per axis)")
-        grid = tuple(int(v) for v in (np.repeat(g, 3) if g.size == 1 else g))
-    out = {"distance": torch.full((N,), float("inf"), dtype=torch.float32, device=dev),
-           "d2": torch.full((N,), float("inf"), dtype=torch.float64, device=dev), "face": torch.full((N,), -1, dtype=torch.int32, device=dev),
-           "closest": torch.full((N, 3), float("nan"), dtype=torch.float32, device=dev),
-           "bary": torch.full((N, 3), float("nan"), dtype=torch.float32, device=dev), "counts": dict.fromkeys(_DIST_COUNTS, 0),
-           "grid": grid if grid is not None else (1, 1, 1)}
+    grid = _dist_grid_arg(who, grid)
+    out = _dist_empty(N, dev, grid)
     if N == 0:
         return out
     if V == 0 or F == 0:
@@ -839,61 +834,95 @@ def closest_points(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tenso
         out["distance"][bad], out["d2"][bad] = float("nan"), float("nan")
         out["counts"]["non_finite_queries"] = int(bad.sum())
         return out
-    L = lib.load()
-    i64 = dict(dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        stream = lib.stream()
-        bad = torch.zeros(1, **i64)
-        lib.check(L.mofa_cc_validate(faces.data_ptr(), F, V, bad.data_ptr(), stream), "mofa_cc_validate")
-        n_bad = int(bad.cpu()[0])
-        if n_bad:
-            raise lib.MofaError(f"{who}: {n_bad} of the {3 * F} face indices lie outside [0, {V})")
-        bad.zero_()
-        lib.check(L.mofa_dist_validate(lib.ptr(verts), V, bad.data_ptr(), stream), "mofa_dist_validate")
-        n_bad = int(bad.cpu()[0])
-        if n_bad:
-            raise lib.MofaError(f"{who}: {n_bad} of the {3 * V} coordinates of the target mesh are not finite")
-        box = torch.stack([verts.amin(0), verts.amax(0)]).cpu().numpy()
-        if grid is None:
-            grid = default_dist_grid(box[0], box[1], F)
-        out["grid"] = grid
-        origin, cell, slack = dist_grid(box[0], box[1], grid)
-        o3, c3, s3, n3 = _d3(origin), _d3(cell), _d3(slack), (C.c_int32 * 3)(*grid)
-        n_cells = grid[0] * grid[1] * grid[2]
-        counts = torch.zeros(len(_DIST_COUNTS), **i64)
-        per_face = torch.empty(F, **i64)
-        lib.check(L.mofa_dist_bin_count(lib.ptr(verts), faces.data_ptr(), F, V, o3, c3, s3, n3, per_face.data_ptr(), counts.data_ptr(), stream),
-                  "mofa_dist_bin_count")
-        ends = torch.cumsum(per_face, 0)
-        P = int(ends[-1].cpu())
-        if P > INT32_MAX:
-            raise lib.MofaError(f"{who}: the {F} faces enter {P} cells of the {grid} grid, more than 2^31 - 1: take a coarser grid")
-        start = torch.zeros(n_cells + 1, dtype=torch.int32, device=dev)
-        pair_face = torch.empty(P, dtype=torch.int32, device=dev)
-        if P:
-            offsets = (ends - per_face).contiguous()
-            pair_cell = torch.empty(P, dtype=torch.int32, device=dev)
-            lib.check(L.mofa_dist_bin_emit(lib.ptr(verts), faces.data_ptr(), F, V, o3, c3, s3, n3, offsets.data_ptr(), P, pair_cell.data_ptr(),
-                                           pair_face.data_ptr(), stream), "mofa_dist_bin_emit")
-            if n_cells > 1:
-                by_cell = torch.sort(pair_cell, stable=True).indices
-                pair_face = pair_face[by_cell].contiguous()
-                del by_cell
-            start[1:] = torch.cumsum(torch.bincount(pair_cell.long(), minlength=n_cells), 0).to(torch.int32)
-            del pair_cell, offsets
-        order = None
-        if n_cells > 1:                          # queries of one cell next to each other: a wavefront's lanes walk the same neighbourhood
-            t = torch.nan_to_num((points.double() - torch.from_numpy(origin).to(dev)) / torch.from_numpy(cell).to(dev), nan=0.0, posinf=0.0,
-                                 neginf=0.0).floor_()
-            hi = torch.tensor([g - 1 for g in grid], dtype=torch.float64, device=dev)
-            c = torch.minimum(torch.clamp_(t, min=0.0), hi).long()
-            order = torch.argsort((c[:, 0] * grid[1] + c[:, 1]) * grid[2] + c[:, 2])
-            del t, c
-        lib.check(L.mofa_dist_query(lib.ptr(points), N, None if order is None else order.data_ptr(), lib.ptr(verts), V, faces.data_ptr(), F, o3, c3,
-                                    s3, n3, start.data_ptr(), pair_face.data_ptr() if P else None, P, maxd, lib.ptr(out["distance"]),
-                                    out["d2"].data_ptr(), out["face"].data_ptr(), lib.ptr(out["closest"]), lib.ptr(out["bary"]),
-                                    counts.data_ptr(), stream), "mofa_dist_query")
-        out["counts"] = dict(zip(_DIST_COUNTS, (int(v) for v in counts.cpu())))
+        return _dist_query(points, N, verts, faces, V, F, _dist_lists(who, verts, faces, V, F, grid), maxd)
+
+
+def _dist_grid_arg(who, grid):
+    """closest_points' ``grid`` argument as None or a triple, checked."""
+    if grid is None:
+        return None
+    g = np.asarray(grid).reshape(-1)
+    if g.size not in (1, 3) or g.dtype.kind not in "iu" or (g < 1).any() or (g > DIST_GRID_CAP).any():
+        raise lib.MofaError(f"{who}: grid = {grid!r} (want None, an integer or three, 1 .. {DIST_GRID_CAP} per axis)")
+    return tuple(int(v) for v in (np.repeat(g, 3) if g.size == 1 else g))
+
+
+def _dist_empty(N, dev, grid):
+    return {"distance": torch.full((N,), float("inf"), dtype=torch.float32, device=dev),
+            "d2": torch.full((N,), float("inf"), dtype=torch.float64, device=dev), "face": torch.full((N,), -1, dtype=torch.int32, device=dev),
+            "closest": torch.full((N, 3), float("nan"), dtype=torch.float32, device=dev),
+            "bary": torch.full((N, 3), float("nan"), dtype=torch.float32, device=dev), "counts": dict.fromkeys(_DIST_COUNTS, 0),
+            "grid": grid if grid is not None else (1, 1, 1)}
+
+
+def _dist_lists(who, verts, faces, V, F, grid):
+    """The face lists of closest_points (V, F >= 1): the mesh validated, then binned at ``grid`` (None: default_dist_grid).  ``counts`` holds
+    what the binning counted; every query starts from a copy of it."""
+    L, dev = lib.load(), verts.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    stream = lib.stream()
+    bad = torch.zeros(1, **i64)
+    lib.check(L.mofa_cc_validate(faces.data_ptr(), F, V, bad.data_ptr(), stream), "mofa_cc_validate")
+    n_bad = int(bad.cpu()[0])
+    if n_bad:
+        raise lib.MofaError(f"{who}: {n_bad} of the {3 * F} face indices lie outside [0, {V})")
+    bad.zero_()
+    lib.check(L.mofa_dist_validate(lib.ptr(verts), V, bad.data_ptr(), stream), "mofa_dist_validate")
+    n_bad = int(bad.cpu()[0])
+    if n_bad:
+        raise lib.MofaError(f"{who}: {n_bad} of the {3 * V} coordinates of the target mesh are not finite")
+    box = torch.stack([verts.amin(0), verts.amax(0)]).cpu().numpy()
+    if grid is None:
+        grid = default_dist_grid(box[0], box[1], F)
+    origin, cell, slack = dist_grid(box[0], box[1], grid)
+    o3, c3, s3, n3 = _d3(origin), _d3(cell), _d3(slack), (C.c_int32 * 3)(*grid)
+    n_cells = grid[0] * grid[1] * grid[2]
+    counts = torch.zeros(len(_DIST_COUNTS), **i64)
+    per_face = torch.empty(F, **i64)
+    lib.check(L.mofa_dist_bin_count(lib.ptr(verts), faces.data_ptr(), F, V, o3, c3, s3, n3, per_face.data_ptr(), counts.data_ptr(), stream),
+              "mofa_dist_bin_count")
+    ends = torch.cumsum(per_face, 0)
+    P = int(ends[-1].cpu())
+    if P > INT32_MAX:
+        raise lib.MofaError(f"{who}: the {F} faces enter {P} cells of the {grid} grid, more than 2^31 - 1: take a coarser grid")
+    start = torch.zeros(n_cells + 1, dtype=torch.int32, device=dev)
+    pair_face = torch.empty(P, dtype=torch.int32, device=dev)
+    if P:
+        offsets = (ends - per_face).contiguous()
+        pair_cell = torch.empty(P, dtype=torch.int32, device=dev)
+        lib.check(L.mofa_dist_bin_emit(lib.ptr(verts), faces.data_ptr(), F, V, o3, c3, s3, n3, offsets.data_ptr(), P, pair_cell.data_ptr(),
+                                       pair_face.data_ptr(), stream), "mofa_dist_bin_emit")
+        if n_cells > 1:
+            by_cell = torch.sort(pair_cell, stable=True).indices
+            pair_face = pair_face[by_cell].contiguous()
+            del by_cell
+        start[1:] = torch.cumsum(torch.bincount(pair_cell.long(), minlength=n_cells), 0).to(torch.int32)
+        del pair_cell, offsets
+    return {"grid": grid, "box": box, "origin": origin, "cell": cell, "args": (o3, c3, s3, n3), "start": start, "pair_face": pair_face, "P": P,
+            "counts": counts, "n_cells": n_cells}
+
+
+def _dist_query(points, N, verts, faces, V, F, b, maxd):
+    """closest_points' result (N >= 1) through the lists ``b`` of :func:`_dist_lists`."""
+    L, dev = lib.load(), verts.device
+    out = _dist_empty(N, dev, b["grid"])
+    grid, n_cells, P = b["grid"], b["n_cells"], b["P"]
+    o3, c3, s3, n3 = b["args"]
+    counts = b["counts"].clone()
+    order = None
+    if n_cells > 1:                          # queries of one cell next to each other: a wavefront's lanes walk the same neighbourhood
+        t = torch.nan_to_num((points.double() - torch.from_numpy(b["origin"]).to(dev)) / torch.from_numpy(b["cell"]).to(dev), nan=0.0, posinf=0.0,
+                             neginf=0.0).floor_()
+        hi = torch.tensor([g - 1 for g in grid], dtype=torch.float64, device=dev)
+        c = torch.minimum(torch.clamp_(t, min=0.0), hi).long()
+        order = torch.argsort((c[:, 0] * grid[1] + c[:, 1]) * grid[2] + c[:, 2])
+        del t, c
+    lib.check(L.mofa_dist_query(lib.ptr(points), N, None if order is None else order.data_ptr(), lib.ptr(verts), V, faces.data_ptr(), F, o3, c3,
+                                s3, n3, b["start"].data_ptr(), b["pair_face"].data_ptr() if P else None, P, maxd, lib.ptr(out["distance"]),
+                                out["d2"].data_ptr(), out["face"].data_ptr(), lib.ptr(out["closest"]), lib.ptr(out["bary"]),
+                                counts.data_ptr(), lib.stream()), "mofa_dist_query")
+    out["counts"] = dict(zip(_DIST_COUNTS, (int(v) for v in counts.cpu())))
     return out
 
 
@@ -1838,6 +1867,446 @@ def smooth(verts: torch.Tensor, faces: torch.Tensor, iterations: int = 10, lam: 
         times.pop("start")
         stats["times"] = times
     return src, stats
+
+
+ICP_TERMS = 36           # MOFA_ICP_TERMS: the 28 + 7 + 1 sums of a step
+ICP_CHUNK = 1024         # MOFA_ICP_CHUNK: rows per first-level sum
+ICP_MAX_ITERATIONS = 10000
+_ICP_METRIC = {"point": 0, "plane": 1}                                                                          # MOFA_ICP_POINT / _PLANE
+_ICP_MODEL = {"translation": (3, 4, 5), "rigid": (0, 1, 2, 3, 4, 5), "similarity": (0, 1, 2, 3, 4, 5, 6)}       # the unknowns solved for
+_ICP_IDENTITY = (1.0, (1.0, 0.0, 0.0, 0.0), (0.0, 0.0, 0.0))
+
+
+# ---- the host side of a registration step: plain IEEE fp64 (+ - * / sqrt), every operation in the order DESIGN 3.22 writes down ----------
+def _quat_unit(q):
+    n = math.sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3])
+    return (q[0] / n, q[1] / n, q[2] / n, q[3] / n)
+
+
+def _quat_mul(a, b):
+    return (((a[0] * b[0] - a[1] * b[1]) - a[2] * b[2]) - a[3] * b[3], ((a[0] * b[1] + a[1] * b[0]) + a[2] * b[3]) - a[3] * b[2],
+            ((a[0] * b[2] - a[1] * b[3]) + a[2] * b[0]) + a[3] * b[1], ((a[0] * b[3] + a[1] * b[2]) - a[2] * b[1]) + a[3] * b[0])
+
+
+def _quat_rotation(q):
+    w, x, y, z = q
+    return (1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
+            2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
+            2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y))
+
+
+def _rotation_quat(R):
+    """The unit quaternion of a rotation matrix (9 floats, row-major) by Shepperd's choice of the largest pivot."""
+    tr = (R[0] + R[4]) + R[8]
+    if tr > 0.0:
+        S = math.sqrt(tr + 1.0) * 2.0
+        q = (0.25 * S, (R[7] - R[5]) / S, (R[2] - R[6]) / S, (R[3] - R[1]) / S)
+    elif R[0] > R[4] and R[0] > R[8]:
+        S = math.sqrt(((1.0 + R[0]) - R[4]) - R[8]) * 2.0
+        q = ((R[7] - R[5]) / S, 0.25 * S, (R[1] + R[3]) / S, (R[2] + R[6]) / S)
+    elif R[4] > R[8]:
+        S = math.sqrt(((1.0 + R[4]) - R[0]) - R[8]) * 2.0
+        q = ((R[2] - R[6]) / S, (R[1] + R[3]) / S, 0.25 * S, (R[5] + R[7]) / S)
+    else:
+        S = math.sqrt(((1.0 + R[8]) - R[0]) - R[4]) * 2.0
+        q = ((R[3] - R[1]) / S, (R[2] + R[6]) / S, (R[5] + R[7]) / S, 0.25 * S)
+    return _quat_unit(q)
+
+
+def _icp_solve(sums, unknowns):
+    """The step ``x [7]`` (zeros outside ``unknowns``) of ``(sum A) x = -(sum g)`` restricted to ``unknowns``, by Cholesky; None when a pivot
+    is not positive and finite, or the solution is not finite."""
+    H = [[0.0] * 7 for _ in range(7)]
+    k = 0
+    for a in range(7):
+        for b in range(a, 7):
+            H[a][b] = H[b][a] = sums[k]
+            k += 1
+    n = len(unknowns)
+    Lm = [[0.0] * n for _ in range(n)]
+    for j in range(n):
+        s = H[unknowns[j]][unknowns[j]]
+        for k in range(j):
+            s = s - Lm[j][k] * Lm[j][k]
+        if not (s > 0.0 and math.isfinite(s)):
+            return None
+        Lm[j][j] = math.sqrt(s)
+        for i in range(j + 1, n):
+            s = H[unknowns[i]][unknowns[j]]
+            for k in range(j):
+                s = s - Lm[i][k] * Lm[j][k]
+            Lm[i][j] = s / Lm[j][j]
+    z = [0.0] * n
+    for i in range(n):
+        s = -sums[28 + unknowns[i]]
+        for k in range(i):
+            s = s - Lm[i][k] * z[k]
+        z[i] = s / Lm[i][i]
+    x = [0.0] * n
+    for i in range(n - 1, -1, -1):
+        s = z[i]
+        for k in range(i + 1, n):
+            s = s - Lm[k][i] * x[k]
+        x[i] = s / Lm[i][i]
+    if not all(math.isfinite(v) for v in x):
+        return None
+    full = [0.0] * 7
+    for j, i in enumerate(unknowns):
+        full[i] = x[j]
+    return full
+
+
+def _icp_compose(state, x, mu):
+    """(s, q, t) after the step ``x`` about the pivot ``mu``; None when the step's scale 1 + sigma is not positive."""
+    s, q, t = state
+    ds = 1.0 + x[6]
+    if not ds > 0.0:
+        return None
+    dq = _quat_unit((1.0, 0.5 * x[0], 0.5 * x[1], 0.5 * x[2]))
+    dR = _quat_rotation(dq)
+    u = (t[0] - mu[0], t[1] - mu[1], t[2] - mu[2])
+    t = tuple((ds * ((dR[3 * r] * u[0] + dR[3 * r + 1] * u[1]) + dR[3 * r + 2] * u[2]) + mu[r]) + x[3 + r] for r in range(3))
+    return ds * s, _quat_unit(_quat_mul(dq, q)), t
+
+
+def _icp_step_size(x, extent):
+    return max(max(abs(x[0]), abs(x[1]), abs(x[2])), max(abs(x[3]), abs(x[4]), abs(x[5])) / extent, abs(x[6]))
+
+
+def _icp_extent(box):
+    """(the centre [3], the largest edge or 1) of a float32 box [2,3], in fp64."""
+    lo, hi = (np.asarray(b, dtype=np.float32).astype(np.float64) for b in box)
+    extent = float((hi - lo).max())
+    return tuple(float(v) for v in (lo + hi) * 0.5), extent if extent > 0.0 else 1.0
+
+
+def _icp_init(who, init):
+    """``init`` (None, a result dict of fit_transform / register, or a 4 x 4 similarity matrix) as (s, q, t)."""
+    if init is None:
+        return _ICP_IDENTITY
+    try:
+        if isinstance(init, dict):
+            s = float(init["scale"])
+            R = np.asarray(_host(init["rotation"]), dtype=np.float64).reshape(3, 3)
+            t = np.asarray(_host(init["translation"]), dtype=np.float64).reshape(3)
+        else:
+            M = np.asarray(_host(init), dtype=np.float64).reshape(4, 4)
+            s = math.sqrt((M[0, 0] * M[0, 0] + M[0, 1] * M[0, 1]) + M[0, 2] * M[0, 2])
+            with np.errstate(all="ignore"):
+                R, t = M[:3, :3] / s, M[:3, 3]
+    except (KeyError, TypeError, ValueError) as e:
+        raise lib.MofaError(f"{who}: init = {init!r} (want None, a dict with scale / rotation / translation, or a 4 x 4 matrix): {e}")
+    if not (np.isfinite(s) and s > 0 and np.isfinite(R).all() and np.isfinite(t).all()):
+        raise lib.MofaError(f"{who}: init needs a finite transform with scale > 0")
+    q = _rotation_quat([float(v) for v in R.reshape(-1)])
+    if not all(math.isfinite(v) for v in q):
+        raise lib.MofaError(f"{who}: init's rotation block is no rotation")
+    return s, q, tuple(float(v) for v in t)
+
+
+def _icp_args(who, model, metric, iterations, tol):
+    if model not in _ICP_MODEL:
+        raise lib.MofaError(f"{who}: model = {model!r} (want 'rigid', 'similarity' or 'translation')")
+    if metric not in _ICP_METRIC:
+        raise lib.MofaError(f"{who}: metric = {metric!r} (want 'point' or 'plane')")
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or not 0 <= int(iterations) <= ICP_MAX_ITERATIONS:
+        raise lib.MofaError(f"{who}: iterations = {iterations!r} (want an integer 0 .. {ICP_MAX_ITERATIONS})")
+    tol = float(tol)
+    if not tol >= 0:
+        raise lib.MofaError(f"{who}: tol = {tol} (want >= 0)")
+    return int(iterations), tol
+
+
+def _icp_weight(who, weight, N, dev):
+    if weight is None:
+        return torch.ones(N, dtype=torch.float64, device=dev)
+    if not torch.is_tensor(weight) or not weight.is_cuda:
+        raise lib.MofaError(f"{who}: the HIP path needs tensors on the GPU (got a CPU weight); there is no CPU fallback")
+    if weight.dtype != torch.float64 or weight.shape != (N,) or weight.device != dev:
+        raise lib.MofaError(f"{who}: want float64 weight [{N}] on {dev}, got {weight.dtype} {tuple(weight.shape)} on {weight.device}")
+    if N and not bool((weight >= 0).all()):
+        raise lib.MofaError(f"{who}: the weights must be >= 0 (and not NaN)")
+    return weight.contiguous()
+
+
+def _icp_result(state, moved, history, iterations, status):
+    s, q, t = state
+    R = np.array(_quat_rotation(q), dtype=np.float64).reshape(3, 3)
+    M = np.eye(4)
+    M[:3, :3], M[:3, 3] = s * R, t
+    return {"scale": float(s), "rotation": R, "translation": np.array(t, dtype=np.float64), "matrix": M, "moved": moved, "history": history,
+            "iterations": iterations, "status": status}
+
+
+def _icp_apply(points, N, state, out=None):
+    s, q, t = state
+    out = torch.empty_like(points) if out is None else out
+    T = (C.c_double * 13)(s, *_quat_rotation(q), *t)
+    lib.check(lib.load().mofa_icp_apply(lib.ptr(points), N, T, lib.ptr(out), lib.stream()), "mofa_icp_apply")
+    return out
+
+
+def _icp_reduce(rows, M, ncols):
+    """The one row left of ``rows [M, ncols]`` (float64) after mofa_icp_reduce, level by level."""
+    L = lib.load()
+    while M > 1:
+        n = (M + ICP_CHUNK - 1) // ICP_CHUNK
+        out = torch.empty(n, ncols, dtype=torch.float64, device=rows.device)
+        lib.check(L.mofa_icp_reduce(rows.data_ptr(), M, ncols, out.data_ptr(), lib.stream()), "mofa_icp_reduce")
+        rows, M = out, n
+    return rows.reshape(-1)
+
+
+def _icp_sums(moved, target, normals, face, verts, V, faces, F, weight, N, mu, metric):
+    """The 36 sums of a step and the sum of the weights, on the host: 37 floats after one read."""
+    L, dev = lib.load(), moved.device
+    n = (N + ICP_CHUNK - 1) // ICP_CHUNK
+    partial = torch.empty(n, ICP_TERMS, dtype=torch.float64, device=dev)
+    plane = metric == "plane"
+    lib.check(L.mofa_icp_terms_reduce(lib.ptr(moved), lib.ptr(target), lib.ptr(normals) if plane and normals is not None else None,
+                                      face.data_ptr() if plane and face is not None else None, lib.ptr(verts) if verts is not None else None, V,
+                                      faces.data_ptr() if faces is not None else None, F, weight.data_ptr(), N, _d3(mu), _ICP_METRIC[metric],
+                                      partial.data_ptr(), lib.stream()), "mofa_icp_terms_reduce")
+    wsum = torch.empty(n, 1, dtype=torch.float64, device=dev)
+    lib.check(L.mofa_icp_reduce(weight.data_ptr(), N, 1, wsum.data_ptr(), lib.stream()), "mofa_icp_reduce")
+    return [float(v) for v in torch.cat([_icp_reduce(partial, n, ICP_TERMS), _icp_reduce(wsum, n, 1)]).cpu()]
+
+
+def _icp_update(state, sums, unknowns, mu, extent, entry):
+    """One solve and composition: (the new state or None, the status that ends the loop or None); fills ``entry``'s rms and step."""
+    entry["rms"] = math.sqrt(sums[35] / sums[36]) if sums[36] > 0.0 else float("nan")
+    entry["step"] = float("nan")
+    if entry["used"] == 0:
+        return None, "no_correspondences"
+    x = _icp_solve(sums, unknowns)
+    new = None if x is None else _icp_compose(state, x, mu)
+    if new is None:
+        return None, "singular"
+    entry["step"] = _icp_step_size(x, extent)
+    return new, None
+
+
+def transform_points(points: torch.Tensor, scale, rotation, translation) -> torch.Tensor:
+    """``scale · rotation · x + translation`` for every row of ``points [N,3] float32`` on the GPU (``mofa_icp_apply``): the sum of a row of
+    ``rotation`` (3 x 3) left to right, times ``scale``, plus ``translation``, in fp64, rounded once to float32.  ``N == 0`` launches nothing.
+    Raises ``MofaError`` for a CPU tensor, a wrong dtype or shape, or a transform that is not finite."""
+    who = "transform_points"
+    lib.ptr(points)
+    N = _query_points(who, points, points.device)
+    try:
+        s = float(scale)
+        R = np.asarray(_host(rotation), dtype=np.float64).reshape(3, 3)
+        t = np.asarray(_host(translation), dtype=np.float64).reshape(3)
+    except (TypeError, ValueError) as e:
+        raise lib.MofaError(f"{who}: want a scalar scale, a 3 x 3 rotation and a translation of 3: {e}")
+    if not (np.isfinite(s) and np.isfinite(R).all() and np.isfinite(t).all()):
+        raise lib.MofaError(f"{who}: the transform is not finite")
+    out = torch.empty_like(points)
+    if N == 0:
+        return out
+    with torch.cuda.device(points.device):
+        T = (C.c_double * 13)(s, *[float(v) for v in R.reshape(-1)], *[float(v) for v in t])
+        lib.check(lib.load().mofa_icp_apply(lib.ptr(points), N, T, lib.ptr(out), lib.stream()), "mofa_icp_apply")
+    return out
+
+
+def fit_transform(src: torch.Tensor, dst: torch.Tensor, weight: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None,
+                  model: str = "rigid", metric: str = "point", iterations: int = 8, init=None, tol: float = 0.0) -> dict:
+    """The transform ``x -> s R x + t`` that takes the points ``src [N,3] float32`` onto their partners ``dst [N,3] float32`` (landmarks: row
+    i of one belongs to row i of the other), by the estimation step of :func:`register` — the same kernels, the same host solve — run
+    ``iterations`` times from ``init``; its result is a good ``init`` for :func:`register`.  ``model``: ``"translation"``, ``"rigid"`` or
+    ``"similarity"``; ``metric="plane"`` measures along ``normals [N,3] float32`` (unit normals at ``dst``, taken as they are).  ``weight [N]
+    float64`` (>= 0; 0 leaves a pair out).  A pair with a non-finite coordinate is left out and counted.  The pivot is the centre of
+    ``dst``'s box.  Returns what :func:`register` returns.  ``N == 0``: the identity (or ``init``), ``status="empty"``, no launch."""
+    who = "fit_transform"
+    lib.ptr(src), lib.ptr(dst)
+    N = _query_points(who, src, src.device)
+    dev = src.device
+    if _query_points(who, dst, dev) != N:
+        raise lib.MofaError(f"{who}: {N} source points, {dst.shape[0]} partners")
+    iterations, tol = _icp_args(who, model, metric, iterations, tol)
+    if metric == "plane":
+        if normals is None:
+            raise lib.MofaError(f"{who}: the plane metric needs normals [N,3]")
+        if _query_points(who, normals, dev) != N:
+            raise lib.MofaError(f"{who}: {N} points, {normals.shape[0]} normals")
+    weight = _icp_weight(who, weight, N, dev)
+    state = _icp_init(who, init)
+    if N == 0:
+        return _icp_result(state, torch.empty_like(src), [], 0, "empty")
+    history, status, done = [], "iterations", 0
+    with torch.cuda.device(dev):
+        finite = torch.isfinite(dst).all(1)
+        mu, extent = _icp_extent(torch.stack([dst[finite].amin(0), dst[finite].amax(0)]).cpu().numpy()) if bool(finite.any()) else ((0.0,) * 3, 1.0)
+        moved = torch.empty_like(src)
+        for _ in range(iterations):
+            _icp_apply(src, N, state, moved)
+            ok = finite & torch.isfinite(moved).all(1)
+            w = torch.where(ok, weight, torch.zeros_like(weight))
+            used, bad = (int(v) for v in torch.stack([(w > 0).sum(), (~ok).sum()]).cpu())
+            entry = {"used": used, "rejected": {"non_finite": bad}}
+            history.append(entry)
+            sums = _icp_sums(moved, dst, normals, None, None, 0, None, 0, w, N, mu, metric)
+            new, stop = _icp_update(state, sums, _ICP_MODEL[model], mu, extent, entry)
+            if stop:
+                status = stop
+                break
+            state, done = new, done + 1
+            if entry["step"] <= tol:
+                status = "converged"
+                break
+        _icp_apply(src, N, state, moved)
+    return _icp_result(state, moved, history, done, status)
+
+
+def _border_flags(who, faces, V, F):
+    """(face_border [F] uint8: bit k = the edge opposite corner k is used once over both directions; vert_border [V] uint8)."""
+    adj = _adjacency(who, faces, V, F)
+    run = adj["seg"][1:] - adj["seg"][:-1]
+    entry = adj["perm"][torch.repeat_interleave(run, run) == 1]
+    corner = entry[(entry & 1) == 0] >> 1                       # both directions of a border edge are runs of one: take dir 0
+    bits = torch.zeros(F, 3, dtype=torch.uint8, device=faces.device)
+    bits.view(-1)[corner] = 1
+    return (bits[:, 0] | (bits[:, 1] << 1) | (bits[:, 2] << 2)).contiguous(), adj["boundary"].to(torch.uint8).contiguous()
+
+
+def register(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, model: str = "rigid", metric: str = "plane", iterations: int = 30,
+             init=None, weight: Optional[torch.Tensor] = None, max_distance=None, trim=None, reject_border: bool = True, tol: float = 0.0,
+             pivot=None, grid=None, timing: bool = False) -> dict:
+    """Registers the points ``points [N,3] float32`` onto the triangle mesh ``(verts [V,3] float32, faces [F,3] int32)`` by iterated closest
+    points on the GPU: finds ``x -> s R x + t`` (``model``: ``"translation"``, ``"rigid"``, ``"similarity"``) such that the moved points lie on
+    the mesh.  The target is binned once (closest_points' grid; ``grid`` as there: it changes no bit); every iteration then
+
+    1. moves the points (``mofa_icp_apply``),
+    2. finds their exact closest points (``mofa_dist_query``, bounded by ``max_distance``),
+    3. rejects a correspondence that is not finite, has no face (with ``max_distance``: lies beyond it) or — ``reject_border`` — whose closest
+       point lies on a border edge or border vertex of the mesh (``mofa_icp_reject``: where an open mesh ends, the closest point of
+       everything past the end is the rim, and those pairs pull the fit inwards),
+    4. ``trim`` in (0, 1]: of the n correspondences left with a weight > 0 keeps those whose squared distance is at most the
+       ``ceil(trim n)``-th smallest (ties all kept),
+    5. sums the normal equations of the linearised step about ``pivot`` (None: the centre of the mesh's box) in a fixed order
+       (``mofa_icp_terms_reduce`` / ``mofa_icp_reduce``): ``metric="plane"`` measures along the closest face's normal and converges
+       quadratically near the answer, ``"point"`` measures the full offset and converges linearly,
+    6. solves them on the host by Cholesky and composes the transform through a unit quaternion; no transcendental is involved, so the
+       whole loop is a fixed sequence of IEEE operations: the same input gives the same bytes.
+
+    ``weight [N] float64`` (>= 0): a point of weight 0 is moved but left out of the fit.  Returns a dict: ``scale`` (float), ``rotation
+    [3,3]``, ``translation [3]``, ``matrix [4,4]`` (NumPy float64), ``moved [N,3] float32``, ``history`` (per iteration: ``rms`` — weighted, of
+    the residuals the step was computed from —, ``used``, ``rejected`` by cause, ``step`` = max(|omega|, |tau| / extent, |sigma|)),
+    ``iterations`` (steps taken) and ``status``: ``"converged"`` (step <= ``tol``), ``"iterations"``, ``"singular"`` (a pivot of the Cholesky
+    factor is not positive — a plane lets the points slide — or the step's scale is not; the last transform is kept),
+    ``"no_correspondences"`` (also a mesh without faces) or ``"empty"`` (``N == 0``: the identity, or ``init``, and no launch).  ``timing=True``
+    adds ``times``: seconds of ``bin`` and, summed over the iterations, of ``query``, ``terms`` (steps 3 - 5) and ``host``, each ended by a
+    device synchronisation.  A local method: it finds the nearest minimum, so start it from :func:`fit_transform` of a few landmarks when the
+    meshes are far apart.
+
+    Raises ``MofaError`` for CPU tensors, wrong dtypes or shapes, a face index outside the mesh, a non-finite target vertex, negative
+    weights, ``trim`` outside (0, 1], ``max_distance`` not > 0, an unknown model or metric and a grid out of range."""
+    who = "register"
+    V, F, dev = _mesh_tensors(who, verts, faces)
+    N = _query_points(who, points, dev)
+    iterations, tol = _icp_args(who, model, metric, iterations, tol)
+    maxd = _max_distance(who, max_distance)
+    grid = _dist_grid_arg(who, grid)
+    if trim is not None:
+        trim = float(trim)
+        if not 0.0 < trim <= 1.0:
+            raise lib.MofaError(f"{who}: trim = {trim} (want in (0, 1], or None)")
+    if pivot is not None:
+        pivot = tuple(float(v) for v in np.asarray(pivot, dtype=np.float64).reshape(3))
+        if not all(math.isfinite(v) for v in pivot):
+            raise lib.MofaError(f"{who}: pivot = {pivot} (want finite)")
+    weight = _icp_weight(who, weight, N, dev)
+    state = _icp_init(who, init)
+    if N == 0:
+        return _icp_result(state, points.clone(), [], 0, "empty")
+    if V == 0 or F == 0:
+        with torch.cuda.device(dev):
+            return _icp_result(state, _icp_apply(points, N, state), [], 0, "no_correspondences")
+    history, status, done, times = [], "iterations", 0, dict.fromkeys(("bin", "query", "terms", "host"), 0.0)
+
+    def lap(name, since):
+        if timing:
+            torch.cuda.synchronize(dev)
+            times[name] += time.perf_counter() - since
+        return time.perf_counter()
+
+    with torch.cuda.device(dev):
+        clock = lap("bin", 0.0)
+        times["bin"] = 0.0
+        b = _dist_lists(who, verts, faces, V, F, grid)
+        mu, extent = _icp_extent(b["box"])
+        mu = pivot if pivot is not None else mu
+        if reject_border:
+            face_border, vert_border = _border_flags(who, faces, V, F)
+            border = torch.empty(N, dtype=torch.uint8, device=dev)
+        clock = lap("bin", clock)
+        moved = torch.empty_like(points)
+        zero = torch.zeros_like(weight)
+        for _ in range(iterations):
+            _icp_apply(points, N, state, moved)
+            res = _dist_query(moved, N, verts, faces, V, F, b, maxd)
+            clock = lap("query", clock)
+            finite = torch.isfinite(moved).all(1) & (torch.isfinite(res["d2"]) | (res["face"] < 0))
+            has = finite & (res["face"] >= 0)
+            ok = has
+            if reject_border:
+                lib.check(lib.load().mofa_icp_reject(res["face"].data_ptr(), lib.ptr(res["bary"]), N, faces.data_ptr(), F, V, face_border.data_ptr(),
+                                                     vert_border.data_ptr(), border.data_ptr(), lib.stream()), "mofa_icp_reject")
+                on_border = has & (border != 0)
+                ok = has & ~on_border
+            else:
+                on_border = torch.zeros_like(has)
+            valid = ok & (weight > 0)
+            keep = valid
+            if trim is not None:
+                d2v = res["d2"][valid]
+                if d2v.numel():
+                    k = min(max(int(math.ceil(trim * d2v.numel())), 1), d2v.numel())
+                    keep = valid & (res["d2"] <= torch.sort(d2v).values[k - 1])          # (a value: no order of equal elements enters)
+            w = torch.where(keep, weight, zero)
+            n_used, n_bad, n_none, n_border, n_valid = (int(v) for v in torch.stack([keep.sum(), (~finite).sum(), (finite & ~has).sum(),
+                                                                                     on_border.sum(), valid.sum()]).cpu())
+            entry = {"used": n_used, "rejected": {"non_finite": n_bad, "beyond" if max_distance is not None else "no_face": n_none,
+                                                  "border": n_border, "trimmed": n_valid - n_used}}
+            history.append(entry)
+            sums = _icp_sums(moved, res["closest"], None, res["face"], verts, V, faces, F, w, N, mu, metric)
+            clock = lap("terms", clock)
+            new, stop = _icp_update(state, sums, _ICP_MODEL[model], mu, extent, entry)
+            clock = lap("host", clock)
+            if stop:
+                status = stop
+                break
+            state, done = new, done + 1
+            if entry["step"] <= tol:
+                status = "converged"
+                break
+        _icp_apply(points, N, state, moved)
+    out = _icp_result(state, moved, history, done, status)
+    out["grid"] = b["grid"]
+    if timing:
+        out["times"] = times
+    return out
+
+
+def register_meshes(verts_a: torch.Tensor, faces_a: torch.Tensor, verts_b: torch.Tensor, faces_b: torch.Tensor, spacing: float,
+                    max_subdiv: int = 64, **register_kw) -> dict:
+    """Registers mesh a onto mesh b (:func:`register`): the source points are a's surface quadrature (:func:`sample_faces` with ``spacing``
+    and ``max_subdiv``) with its area weights, followed by a's vertices at weight 0 — moved along, left out of the fit.  Returns
+    :func:`register`'s dict (``moved`` holds the samples, then the vertices) plus ``verts [V,3] float32``, a's vertices under the transform,
+    and ``n_samples``."""
+    who = "register_meshes"
+    _mesh_tensors(who, verts_a, faces_a)
+    _mesh_tensors(who, verts_b, faces_b)
+    if "weight" in register_kw:
+        raise lib.MofaError(f"{who}: the weights are the quadrature's; register() takes explicit ones")
+    pts, _, weight = sample_faces(verts_a, faces_a, spacing, max_subdiv)
+    S = int(pts.shape[0])
+    src = torch.cat([pts, verts_a]).contiguous()
+    weight = torch.cat([weight, torch.zeros(verts_a.shape[0], dtype=torch.float64, device=verts_a.device)])
+    out = register(src, verts_b, faces_b, weight=weight, **register_kw)
+    out["verts"], out["n_samples"] = out["moved"][S:].contiguous(), S
+    return out
 
 
 # faces whose clipped box of samples holds at least this many pixels are walked one wavefront per face (mofa_raster_faces); the choice
