@@ -688,6 +688,72 @@ int mofa_icp_reduce(const double* in, int64_t M, int32_t ncols, double* out, voi
 int mofa_icp_reject(const int32_t* face, const float* bary, int64_t N, const int32_t* faces, int64_t F, int64_t V, const uint8_t* face_border,
                     const uint8_t* vert_border, uint8_t* rejected, void* stream);
 
+/* Non-rigid mesh registration: the linear step of stiffness-regularised ICP with one translation per template vertex (mesh.py drives the
+ * loop: mesh.warp, mesh.warp_to; the correspondences come from mofa_dist_query, the border rule from mofa_icp_reject, the adjacency is
+ * mofa_smooth_step's: offsets [V + 1] (int64), nbr [E] (int32); 1 <= V <= 2^31 - 1, 0 <= E <= 2^31 - 1).  The template is verts v [V,3]
+ * (float), the unknown a displacement d [V,3] (double).  One step minimises
+ *     sum_i w_i rho_i(v_i + d_i - c_i)  +  alpha sum_{edges {i,j}} |d_i - d_j|^2  +  sum_i h_i |v_i + d_i - p_i|^2
+ * whose normal equations are (D + alpha L (x) I3) d = b, D_i a symmetric 3 x 3 block per vertex, L_ii = deg_i, L_ij = -1 for neighbours.
+ * No atomics of any kind and a fixed summation order that does not depend on the launch geometry: the same input gives the same bytes every
+ * time.  No kernel waits on another thread or workgroup.  Every kernel checks the indices it dereferences.  All arithmetic is fp64 (fp32
+ * inputs widened first), every operation rounded separately (no FMA).
+ *   mofa_warp_apply   out [V,3] (float):  out[i][k] = (float)((double)verts[i][k] + disp[i][k])
+ *   mofa_warp_system  one thread per vertex i: v = verts[i], y = moved[i], c = target[i], w = weight[i] (double); for the plane metric the unit
+ *                     normal n exactly as mofa_icp_terms takes it (`face` [V] on the target mesh tverts / tfaces, or `normals` [V,3]).
+ *                       u_k = (double)c_k - (double)v_k;   r_k = (double)y_k - (double)c_k;   rr = (r_0 r_0 + r_1 r_1) + r_2 r_2
+ *                       MOFA_ICP_POINT:  D_kk = w, D_kl = 0;  b_k = w * u_k;  e = w * rr
+ *                       MOFA_ICP_PLANE:  D_kk = w * (n_k * n_k + point_weight),  D_kl = w * (n_k * n_l)  (k < l);
+ *                                        nu = (n_0 u_0 + n_1 u_1) + n_2 u_2;   b_k = w * (n_k * nu + point_weight * u_k);
+ *                                        nr = (n_0 r_0 + n_1 r_1) + n_2 r_2;   e = w * (nr * nr + point_weight * rr)
+ *                     The data term is rejected — D, b, e exact +0.0 — when `w > 0` is false or (plane, by face) the face or one of its
+ *                     vertices lies outside the target mesh.  Then, with handle_weight [V] (double; NULL: none) and h = handle_weight[i] > 0:
+ *                       D_kk += h;   b_k += h * ((double)handle_pos[i][k] - (double)v_k)
+ *                     and with deg = offsets[i + 1] - offsets[i]:   m_k = D_kk + alpha * (double)deg;   minv_k = m_k > 0 ? 1.0 / m_k : 0.0.
+ *                     Outputs: D [V,6] (xx, xy, xz, yy, yz, zz), b [V,3], minv [V,3], energy [V] (e), all double.  A vertex whose list does
+ *                     not lie in [0, E) gets deg = 0 and minv = 0 and is counted: bad [ceil(V / 256)] (int64) holds the count of each
+ *                     workgroup of 256 vertices (written, not added to).
+ *   mofa_warp_matvec  q = (D + alpha L (x) I3) p, one thread per vertex i over nbr[offsets[i] .. offsets[i + 1]) in that order:
+ *                       s_k = 0.0;  s_k += p[j][k];   deg = (double)(offsets[i + 1] - offsets[i])
+ *                       q_0 = ((D_xx p_0 + D_xy p_1) + D_xz p_2) + alpha * (deg * p_0 - s_0)
+ *                       q_1 = ((D_xy p_0 + D_yy p_1) + D_yz p_2) + alpha * (deg * p_1 - s_1)
+ *                       q_2 = ((D_xz p_0 + D_yz p_1) + D_zz p_2) + alpha * (deg * p_2 - s_2)
+ *                     and partial [ceil(V / MOFA_ICP_CHUNK)] = the first level of p . q (mofa_warp_dot's, fused).  A vertex with a list outside
+ *                     [0, E) or a neighbour outside [0, V) writes nothing, adds nothing to the sum and is counted: bad [ceil(V /
+ *                     MOFA_ICP_CHUNK)] (int64) holds the count of each chunk (written).  p != q.
+ *   mofa_warp_dot     partial [ceil(V / MOFA_ICP_CHUNK)] (double): the first level of the sum of term_i = (a_0 b_0 + a_1 b_1) + a_2 b_2 over
+ *                     the rows of a, b [V,3] (double), exactly as mofa_icp_reduce sums a one-column matrix of the terms; the caller
+ *                     reduces the partial sums with mofa_icp_reduce (ncols = 1) until one number is left.
+ *   mofa_warp_solve   Jacobi-preconditioned conjugate gradients on A = D + alpha L (x) I3 from the start x [V,3] (double, in and out):
+ *                       q = A x;  r = b - q;  z = minv * r (per component);  p = z;  rho_0 = r . z
+ *                       step s = 0 .. K - 1:   q = A p;  pq = p . q;  [scalar]  a = rho_s / pq;
+ *                                              x += a * p;  r = r - a * q;  z = minv * r;  rho_{s+1} = r . z;  p = z + (rho_{s+1} / rho_s) * p
+ *                     every inner product by mofa_warp_dot's sum, its first level fused into the kernel that writes the vectors.  [scalar] is
+ *                     one thread: the solve FREEZES at step s when rho_s <= cg_tol^2 * rho_0 (MOFA_WARP_STOP_TOLERANCE), else when
+ *                     `pq > 0` is false (MOFA_WARP_STOP_BREAKDOWN).  The flag lives in device memory and is sticky: from then on no step
+ *                     writes x, r, z, p or q, so every vector keeps its bits, and rho_{s+1} = rho_s.  The K steps are enqueued without a
+ *                     host read or a synchronisation.  rec [MOFA_WARP_REC_RHO + K + 1] (double, DEVICE; cleared by the solve):
+ *                     rec[MOFA_WARP_REC_A] the last a (0 once frozen), _FROZEN 0 / 1, _CAUSE 0 or MOFA_WARP_STOP_*, _STEPS the steps that
+ *                     moved x, _TOL2 = cg_tol * cg_tol, rec[MOFA_WARP_REC_RHO + s] = rho_s for s = 0 .. K.  work holds
+ *                     mofa_warp_workspace_doubles(V) doubles (r, z, p, q and the levels of the two sums); bad as mofa_warp_matvec's.
+ *                     1 <= cg_iterations <= MOFA_WARP_MAX_CG, 0 <= cg_tol < 1.
+ * A null pointer, a count out of range, an unknown metric, a negative or non-finite alpha / point_weight, the plane metric with both or
+ * neither of face / normals, or handle weights without positions returns MOFA_EINVAL with a message. */
+#define MOFA_WARP_MAX_CG 10000
+enum { MOFA_WARP_REC_A = 0, MOFA_WARP_REC_FROZEN = 1, MOFA_WARP_REC_CAUSE = 2, MOFA_WARP_REC_STEPS = 3, MOFA_WARP_REC_TOL2 = 4,
+       MOFA_WARP_REC_RHO = 8 };
+enum { MOFA_WARP_STOP_TOLERANCE = 1, MOFA_WARP_STOP_BREAKDOWN = 2 };
+int mofa_warp_apply(const float* verts, const double* disp, int64_t V, float* out, void* stream);
+int mofa_warp_system(const float* verts, const float* moved, const float* target, const float* normals, const int32_t* face, const float* tverts,
+                     int64_t TV, const int32_t* tfaces, int64_t TF, const double* weight, const double* handle_weight, const float* handle_pos,
+                     const int64_t* offsets, int64_t E, int64_t V, int32_t metric, double point_weight, double alpha, double* D, double* b,
+                     double* minv, double* energy, int64_t* bad, void* stream);
+int mofa_warp_matvec(const double* D, const double* p, const int64_t* offsets, const int32_t* nbr, int64_t E, int64_t V, double alpha, double* q,
+                     double* partial, int64_t* bad, void* stream);
+int mofa_warp_dot(const double* a, const double* b, int64_t V, double* partial, void* stream);
+size_t mofa_warp_workspace_doubles(int64_t V);
+int mofa_warp_solve(const double* D, const double* b, const double* minv, const int64_t* offsets, const int32_t* nbr, int64_t E, int64_t V,
+                    double alpha, int32_t cg_iterations, double cg_tol, double* x, double* work, double* rec, int64_t* bad, void* stream);
+
 /* ---- occupancy-culled rendering: skip the network where an occupancy grid says the space is empty ---------------------------------
  * The grid lives on the lattice of mofa_grid_points (nx x ny x nz samples at lo + (i,j,k) step): (nx-1)(ny-1)(nz-1) cells, one byte
  * each (0 / 1), cell index (i (ny-1) + j) (nz-1) + k.  The lattice needs 2 <= n < 2^24 per axis and fewer than 2^31 cells.

@@ -118,6 +118,13 @@ SIGNATURES = {
     "mofa_icp_terms_reduce": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i64, _fp, _i64, _fp, _i64, _d3, _i32, _fp, _fp]),
     "mofa_icp_reduce": (C.c_int, [_fp, _i64, _i32, _fp, _fp]),
     "mofa_icp_reject": (C.c_int, [_fp, _fp, _i64, _fp, _i64, _i64, _fp, _fp, _fp, _fp]),
+    "mofa_warp_apply": (C.c_int, [_fp, _fp, _i64, _fp, _fp]),
+    "mofa_warp_system": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _i64, _i64, _i32, C.c_double, C.c_double,
+                                   _fp, _fp, _fp, _fp, _fp, _fp]),
+    "mofa_warp_matvec": (C.c_int, [_fp, _fp, _fp, _fp, _i64, _i64, C.c_double, _fp, _fp, _fp, _fp]),
+    "mofa_warp_dot": (C.c_int, [_fp, _fp, _i64, _fp, _fp]),
+    "mofa_warp_workspace_doubles": (_sz, [_i64]),
+    "mofa_warp_solve": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i64, _i64, C.c_double, _i32, C.c_double, _fp, _fp, _fp, _fp, _fp]),
     "mofa_occ_workspace_bytes": (_sz, [_i64]),
     "mofa_occ_cells": (C.c_int, [_fp, _i64, _i64, _i64, C.c_float, _i32, _fp, _fp]),
     "mofa_occ_dilate": (C.c_int, [_fp, _i64, _i64, _i64, _i32, _fp, _fp, _fp]),

@@ -2309,6 +2309,335 @@ def register_meshes(verts_a: torch.Tensor, faces_a: torch.Tensor, verts_b: torch
     return out
 
 
+WARP_MAX_CG = 10000      # MOFA_WARP_MAX_CG
+WARP_REC_RHO = 8         # MOFA_WARP_REC_RHO: the record's first rho; before it a, frozen, cause, steps, tol^2 (MOFA_WARP_REC_*)
+_WARP_STOPS = {0: "iterations", 1: "tolerance", 2: "breakdown"}       # MOFA_WARP_STOP_*
+
+
+def _warp_args(who, metric, stiffness, point_weight, cg_iterations, cg_tol):
+    """The scalar parameters of warp_to / warp, checked before any tensor is looked at: (the stiffness schedule, point_weight, cg_tol)."""
+    if metric not in _ICP_METRIC:
+        raise lib.MofaError(f"{who}: metric = {metric!r} (want 'point' or 'plane')")
+    try:
+        levels = [float(a) for a in np.asarray(stiffness, dtype=np.float64).reshape(-1)]
+        point_weight, cg_tol = float(point_weight), float(cg_tol)
+    except (TypeError, ValueError):
+        raise lib.MofaError(f"{who}: stiffness = {stiffness!r}, point_weight = {point_weight!r}, cg_tol = {cg_tol!r} (want numbers)") from None
+    if not levels or not all(math.isfinite(a) and a >= 0.0 for a in levels):
+        raise lib.MofaError(f"{who}: stiffness = {stiffness!r} (want one or more finite values >= 0)")
+    if not (point_weight >= 0.0 and math.isfinite(point_weight)):
+        raise lib.MofaError(f"{who}: point_weight = {point_weight} (want finite, >= 0)")
+    if isinstance(cg_iterations, (bool, np.bool_)) or not isinstance(cg_iterations, (int, np.integer)) or not 1 <= int(cg_iterations) <= WARP_MAX_CG:
+        raise lib.MofaError(f"{who}: cg_iterations = {cg_iterations!r} (want an integer 1 .. {WARP_MAX_CG})")
+    if not 0.0 <= cg_tol < 1.0:
+        raise lib.MofaError(f"{who}: cg_tol = {cg_tol} (want in [0, 1))")
+    return levels, point_weight, cg_tol
+
+
+def _warp_template(who, verts, faces, init):
+    """The template of warp_to / warp on the GPU: (V, F, device, the adjacency or None when nobody has a neighbour, the start d [V,3] float64).
+    Refuses a face index outside the mesh and a non-finite vertex that a face references."""
+    V, F, dev = _mesh_tensors(who, verts, faces)
+    if init is not None:
+        if not torch.is_tensor(init) or not init.is_cuda:
+            raise lib.MofaError(f"{who}: the HIP path needs tensors on the GPU (got a CPU init); there is no CPU fallback")
+        if init.dtype != torch.float64 or init.shape != (V, 3) or init.device != dev:
+            raise lib.MofaError(f"{who}: want init = None or a float64 displacement [{V},3] on {dev}, got {init.dtype} {tuple(init.shape)}")
+        if V and not bool(torch.isfinite(init).all()):
+            raise lib.MofaError(f"{who}: init is not finite")
+    d = torch.zeros(V, 3, dtype=torch.float64, device=dev) if init is None else init.clone().contiguous()
+    adj = None
+    if V and F:
+        with torch.cuda.device(dev):
+            adj = _adjacency(who, faces, V, F)
+            referenced = torch.zeros(V, dtype=torch.bool, device=dev)
+            referenced[faces.reshape(-1).long()] = True
+            n_bad = int((referenced & ~torch.isfinite(verts).all(1)).sum())
+        if n_bad:
+            raise lib.MofaError(f"{who}: {n_bad} of the vertices the faces reference have a non-finite coordinate")
+    return V, F, dev, adj, d
+
+
+def _warp_graph(adj, V, dev):
+    """(offsets, neighbours, E) of the template's adjacency; without one every list is empty."""
+    if adj is None:
+        return torch.zeros(V + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev), 0
+    return adj["offsets"], adj["neighbours"], int(adj["neighbours"].shape[0])
+
+
+def _warp_apply(verts, d, V, out):
+    lib.check(lib.load().mofa_warp_apply(lib.ptr(verts), d.data_ptr(), V, lib.ptr(out), lib.stream()), "mofa_warp_apply")
+    return out
+
+
+class _WarpSolver:
+    """The buffers of the per-vertex system and its solve, allocated once per call of warp_to / warp."""
+
+    def __init__(self, V, graph, cg_iterations, cg_tol, dev):
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.V, (self.offsets, self.nbr, self.E), self.K, self.tol = V, graph, cg_iterations, cg_tol
+        self.D, self.b, self.minv, self.energy = torch.empty(V, 6, **f64), torch.empty(V, 3, **f64), torch.empty(V, 3, **f64), torch.empty(V, **f64)
+        self.work = torch.empty(int(lib.load().mofa_warp_workspace_doubles(V)), **f64)
+        self.rec = torch.empty(WARP_REC_RHO + cg_iterations + 1, **f64)
+        self.bad_system = torch.zeros((V + 255) // 256, dtype=torch.int64, device=dev)
+        self.bad_solve = torch.zeros((V + ICP_CHUNK - 1) // ICP_CHUNK, dtype=torch.int64, device=dev)
+
+    def system(self, verts, moved, target, normals, face, tverts, TV, tfaces, TF, weight, hweight, hpos, metric, point_weight, alpha):
+        plane = metric == "plane"
+        lib.check(lib.load().mofa_warp_system(
+            lib.ptr(verts), lib.ptr(moved), lib.ptr(target), lib.ptr(normals) if plane and normals is not None else None,
+            face.data_ptr() if plane and face is not None else None, lib.ptr(tverts) if tverts is not None else None, TV,
+            tfaces.data_ptr() if tfaces is not None else None, TF, weight.data_ptr(), None if hweight is None else hweight.data_ptr(),
+            None if hpos is None else lib.ptr(hpos), self.offsets.data_ptr(), self.E, self.V, _ICP_METRIC[metric], point_weight, alpha,
+            self.D.data_ptr(), self.b.data_ptr(), self.minv.data_ptr(), self.energy.data_ptr(), self.bad_system.data_ptr(), lib.stream()),
+            "mofa_warp_system")
+
+    def solve(self, alpha, x):
+        """Enqueues the whole solve from ``x`` (float64 [V,3], overwritten); nothing is read back here."""
+        lib.check(lib.load().mofa_warp_solve(self.D.data_ptr(), self.b.data_ptr(), self.minv.data_ptr(), self.offsets.data_ptr(),
+                                             self.nbr.data_ptr() if self.E else None, self.E, self.V, alpha, self.K, self.tol, x.data_ptr(),
+                                             self.work.data_ptr(), self.rec.data_ptr(), self.bad_solve.data_ptr(), lib.stream()), "mofa_warp_solve")
+
+    def tail(self):
+        """What the host reads after a solve, still on the device: the record, then the two bad-index counts."""
+        return torch.cat([self.rec, torch.stack([self.bad_system.sum(), self.bad_solve.sum()]).double()])
+
+    def record(self, who, tail):
+        """(rho [K + 1], steps, stop) from the host copy of :meth:`tail`."""
+        n_bad = int(tail[-2]) + int(tail[-1])
+        if n_bad:
+            raise lib.MofaError(f"{who}: {n_bad} indices were out of range inside the solve (the mesh changed while it was warped?)")
+        return tail[WARP_REC_RHO:WARP_REC_RHO + self.K + 1].copy(), int(tail[3]), _WARP_STOPS[int(tail[2])]
+
+
+def warp_to(verts: torch.Tensor, faces: torch.Tensor, targets: torch.Tensor, weight: Optional[torch.Tensor] = None,
+            normals: Optional[torch.Tensor] = None, metric: str = "point", stiffness: float = 1.0, point_weight: float = 1e-2, init=None,
+            cg_iterations: int = 200, cg_tol: float = 1e-8):
+    """Deforms the template ``(verts [V,3] float32, faces [F,3] int32)`` towards explicit per-vertex targets — row i of ``targets [V,3]
+    float32`` belongs to vertex i — by ONE solve of the step :func:`warp` iterates (``mofa_warp_system`` / ``mofa_warp_solve``): the
+    displacement ``d [V,3] float64`` that minimises
+
+        ``sum_i w_i rho_i(v_i + d_i - c_i)  +  stiffness * sum_{edges {i,j}} |d_i - d_j|^2``
+
+    over the undirected edges of :func:`vertex_adjacency`.  ``metric="point"``: ``rho_i(u) = |u|^2``; ``"plane"``: ``(n_i . u)^2 +
+    point_weight |u|^2`` with ``normals [V,3] float32`` (unit normals at the targets, taken as they are; required).  ``weight [V] float64``
+    (>= 0): a vertex of weight 0, or with a non-finite target, follows its neighbours through the stiffness term alone — landmark-driven
+    deformation is this call with weight 0 everywhere but at the landmarks.  The normal equations are solved by Jacobi-preconditioned
+    conjugate gradients from ``init`` (a displacement [V,3] float64; None: zero): exactly ``cg_iterations`` steps are enqueued and the host
+    reads nothing in between; a flag in device memory freezes the solve once ``rho <= cg_tol^2 rho_0`` or the curvature ``p . A p`` is
+    not positive, and a frozen step leaves every vector's bits alone.  Every sum has a fixed order (include/mofanerf_hip.h): the same input
+    gives the same bytes.
+
+    Returns ``(verts' [V,3] float32 = (float)(verts + d), d [V,3] float64, solve)``; ``solve``: ``rho`` (NumPy [cg_iterations + 1]: the
+    preconditioned residual ``r . z`` after 0 .. cg_iterations steps), ``steps`` (those that moved d) and ``stop`` (``"tolerance"``,
+    ``"breakdown"`` or ``"iterations"``).  A vertex without neighbours and without weight keeps its start.  ``V == 0`` launches nothing.
+    ``faces`` and the numbering are never touched.  Raises ``MofaError`` for an unknown metric, a negative or non-finite stiffness or
+    ``point_weight``, ``cg_iterations`` outside 1 .. 10000, ``cg_tol`` outside [0, 1) — all before any tensor is looked at —, CPU tensors,
+    wrong dtypes or shapes, a face index outside the mesh, a non-finite vertex a face references and negative weights."""
+    who = "warp_to"
+    levels, point_weight, cg_tol = _warp_args(who, metric, stiffness, point_weight, cg_iterations, cg_tol)
+    if len(levels) != 1:
+        raise lib.MofaError(f"{who}: stiffness = {stiffness!r} (want one value; warp() takes a schedule)")
+    V, F, dev, adj, d = _warp_template(who, verts, faces, init)
+    if _query_points(who, targets, dev) != V:
+        raise lib.MofaError(f"{who}: {V} vertices, {targets.shape[0]} targets")
+    if metric == "plane":
+        if normals is None:
+            raise lib.MofaError(f"{who}: the plane metric needs normals [V,3]")
+        if _query_points(who, normals, dev) != V:
+            raise lib.MofaError(f"{who}: {V} vertices, {normals.shape[0]} normals")
+    weight = _icp_weight(who, weight, V, dev)
+    if V == 0:
+        return verts.clone(), d, {"rho": np.zeros(0), "steps": 0, "stop": "iterations"}
+    with torch.cuda.device(dev):
+        ok = torch.isfinite(targets).all(1)
+        if metric == "plane":
+            ok &= torch.isfinite(normals).all(1)
+        w = torch.where(ok, weight, torch.zeros_like(weight))
+        solver = _WarpSolver(V, _warp_graph(adj, V, dev), int(cg_iterations), cg_tol, dev)
+        moved = _warp_apply(verts, d, V, torch.empty_like(verts))
+        solver.system(verts, moved, targets, normals, None, None, 0, None, 0, w, None, None, metric, point_weight, levels[0])
+        solver.solve(levels[0], d)
+        rho, steps, stop = solver.record(who, solver.tail().cpu().numpy())
+        _warp_apply(verts, d, V, moved)
+    return moved, d, {"rho": rho, "steps": steps, "stop": stop}
+
+
+def _warp_handles(who, handles, V, dev):
+    """``handles = (index [K], position [K,3] float32, weight: a scalar or [K] float64)`` as dense (weight [V] float64, position [V,3]
+    float32) on the device, or (None, None)."""
+    if handles is None:
+        return None, None
+    try:
+        index, pos, hw = handles
+    except (TypeError, ValueError):
+        raise lib.MofaError(f"{who}: handles = (index [K], position [K,3], weight), got {type(handles).__name__}") from None
+    for name, t in (("index", index), ("position", pos)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise lib.MofaError(f"{who}: the HIP path needs tensors on the GPU (got CPU handle {name}); there is no CPU fallback")
+    if index.dtype not in (torch.int32, torch.int64) or index.dim() != 1 or index.device != dev:
+        raise lib.MofaError(f"{who}: want handle indices [K] int32 or int64 on {dev}, got {index.dtype} {tuple(index.shape)} on {index.device}")
+    K = int(index.shape[0])
+    if pos.dtype != torch.float32 or pos.shape != (K, 3) or pos.device != dev:
+        raise lib.MofaError(f"{who}: want handle positions [{K},3] float32 on {dev}, got {pos.dtype} {tuple(pos.shape)} on {pos.device}")
+    if torch.is_tensor(hw):
+        if hw.dtype != torch.float64 or hw.shape != (K,) or hw.device != dev:
+            raise lib.MofaError(f"{who}: want handle weights a number or [{K}] float64 on {dev}, got {hw.dtype} {tuple(hw.shape)}")
+    else:
+        hw = torch.full((K,), float(hw), dtype=torch.float64, device=dev)
+    index = index.long()
+    if K:
+        if not bool(((index >= 0) & (index < V)).all()):
+            raise lib.MofaError(f"{who}: a handle index lies outside [0, {V})")
+        if int(torch.unique(index).shape[0]) != K:
+            raise lib.MofaError(f"{who}: a handle index is repeated")
+        if not bool(torch.isfinite(pos).all()) or not bool((torch.isfinite(hw) & (hw >= 0)).all()):
+            raise lib.MofaError(f"{who}: the handles need finite positions and finite weights >= 0")
+    hweight, hpos = torch.zeros(V, dtype=torch.float64, device=dev), torch.zeros(V, 3, dtype=torch.float32, device=dev)
+    hweight[index], hpos[index] = hw, pos
+    return hweight, hpos
+
+
+def warp(verts: torch.Tensor, faces: torch.Tensor, target_verts: torch.Tensor, target_faces: torch.Tensor, metric: str = "plane",
+         stiffness=(10.0, 1.0, 0.1), iterations: int = 5, point_weight: float = 1e-2, weight: Optional[torch.Tensor] = None, handles=None,
+         max_distance=None, reject_border: bool = True, init=None, tol: float = 0.0, cg_iterations: int = 200, cg_tol: float = 1e-8, grid=None,
+         timing: bool = False) -> dict:
+    """Warps the template ``(verts [V,3] float32, faces [F,3] int32)`` onto the target mesh ``(target_verts, target_faces)`` without touching
+    its topology — non-rigid registration by stiffness-regularised iterated closest points with one translation per vertex (Amberg-style
+    optimal-step N-ICP) —, so that meshes of different triangulations come out in ONE vertex numbering.  The unknown is a
+    displacement ``d [V,3] float64``; the warped vertex is ``(float)(verts + d)``.  The target is binned once (closest_points' grid; ``grid``
+    as there: it changes no bit).  For every level of the ``stiffness`` schedule, ``iterations`` times:
+
+    1. the template is moved (``mofa_warp_apply``),
+    2. its vertices' exact closest points are found (``mofa_dist_query``, bounded by ``max_distance``),
+    3. a vertex is rejected from the data term when it is not finite, has no face (with ``max_distance``: lies beyond it) or —
+       ``reject_border`` — when its closest point lies on the target's border (``mofa_icp_reject``); a rejected vertex keeps its stiffness
+       rows and its handle,
+    4. the per-vertex system of ``sum_i w_i rho_i(v_i + d_i - c_i) + alpha sum_{edges} |d_i - d_j|^2 + sum_l beta_l |v_l + d_l - p_l|^2`` is
+       built (``mofa_warp_system``; ``metric`` and ``point_weight`` as in :func:`warp_to`, the normal that of the closest face),
+    5. and solved by preconditioned conjugate gradients from the previous d (``mofa_warp_solve``: ``cg_iterations`` steps enqueued, frozen
+       on the device at ``cg_tol``); the host reads one small record per iteration.
+
+    Stiff levels move the template as a near-rigid sheet, loose ones let it take the target's detail.  The stiffness acts on the
+    DISPLACEMENTS: it penalises a rotation of the template as much as a bend, so align first (:func:`register_meshes`).  ``weight [V]
+    float64`` (>= 0) weighs the data term; ``handles = (index [K], position [K,3] float32, weight)`` pins landmark vertices to positions
+    (a repeated index is refused).  A level ends early when ``max_i |delta d_i| <= tol * extent`` (the largest edge of the target's box).
+
+    Returns a dict: ``verts [V,3] float32``, ``displacement [V,3] float64``, ``history`` (per iteration: ``stiffness``, ``rms`` — of the
+    residuals the step was computed from, sqrt(sum w rho / sum w) —, ``used``, ``rejected`` by cause, ``cg_steps``, ``rho`` (the solve's last),
+    ``stop`` and ``step`` = max |delta d_i|), ``iterations`` (solves taken), ``status`` — ``"iterations"``, ``"converged"`` (the last level
+    ended on ``tol``), ``"no_correspondences"`` (no vertex kept; also a target without faces), ``"singular"`` (a solve's first step found
+    ``p . A p > 0`` false with ``rho_0 > 0``; the last d is kept) or ``"empty"`` (``V == 0``: no launch) —, ``grid`` and, with
+    ``timing=True``, ``times``: seconds of ``bin`` and, summed over the iterations, ``query`` (steps 1 - 2), ``system`` (3 - 4) and ``solve``,
+    each ended by a device synchronisation.  Every sum has a fixed order and no transcendental is involved: the same input gives the same
+    bytes.  A local method with no per-vertex rotation, no normal-compatibility test and no colour term.
+
+    Raises ``MofaError`` for the scalar arguments :func:`warp_to` refuses, an empty schedule, ``iterations`` outside 0 .. 10000, ``tol`` < 0
+    (before any tensor is looked at), CPU tensors, wrong dtypes or shapes, face or handle indices outside the mesh, a non-finite template
+    vertex that a face references, a non-finite target vertex or handle, negative weights, ``max_distance`` not > 0 and a grid out of
+    range."""
+    who = "warp"
+    levels, point_weight, cg_tol = _warp_args(who, metric, stiffness, point_weight, cg_iterations, cg_tol)
+    iterations, tol = _icp_args(who, "rigid", metric, iterations, tol)
+    maxd = _max_distance(who, max_distance)
+    grid = _dist_grid_arg(who, grid)
+    V, F, dev, adj, d = _warp_template(who, verts, faces, init)
+    TV, TF, tdev = _mesh_tensors(who, target_verts, target_faces)
+    if tdev != dev:
+        raise lib.MofaError(f"{who}: the template on {dev}, the target on {tdev}")
+    weight = _icp_weight(who, weight, V, dev)
+    hweight, hpos = _warp_handles(who, handles, V, dev)
+
+    def result(moved, history, done, status, g):
+        return {"verts": moved, "displacement": d, "history": history, "iterations": done, "status": status, "grid": g}
+
+    if V == 0:
+        return result(verts.clone(), [], 0, "empty", grid if grid is not None else (1, 1, 1))
+    history, status, done, times = [], "iterations", 0, dict.fromkeys(("bin", "query", "system", "solve"), 0.0)
+
+    def lap(name, since):
+        if timing:
+            torch.cuda.synchronize(dev)
+            times[name] += time.perf_counter() - since
+        return time.perf_counter()
+
+    with torch.cuda.device(dev):
+        moved = torch.empty_like(verts)
+        if TV == 0 or TF == 0:
+            return result(_warp_apply(verts, d, V, moved), [], 0, "no_correspondences", grid if grid is not None else (1, 1, 1))
+        clock = lap("bin", 0.0)
+        times["bin"] = 0.0
+        b = _dist_lists(who, target_verts, target_faces, TV, TF, grid)
+        _, extent = _icp_extent(b["box"])
+        if reject_border:
+            face_border, vert_border = _border_flags(who, target_faces, TV, TF)
+            border = torch.empty(V, dtype=torch.uint8, device=dev)
+        solver = _WarpSolver(V, _warp_graph(adj, V, dev), int(cg_iterations), cg_tol, dev)
+        zero = torch.zeros_like(weight)
+        x = torch.empty_like(d)
+        clock = lap("bin", clock)
+        stopped = None
+        for alpha in levels:
+            status = "iterations"
+            for _ in range(iterations):
+                _warp_apply(verts, d, V, moved)
+                res = _dist_query(moved, V, target_verts, target_faces, TV, TF, b, maxd)
+                clock = lap("query", clock)
+                finite = torch.isfinite(moved).all(1) & (torch.isfinite(res["d2"]) | (res["face"] < 0))
+                has = finite & (res["face"] >= 0)
+                if reject_border:
+                    lib.check(lib.load().mofa_icp_reject(res["face"].data_ptr(), lib.ptr(res["bary"]), V, target_faces.data_ptr(), TF, TV,
+                                                         face_border.data_ptr(), vert_border.data_ptr(), border.data_ptr(), lib.stream()),
+                              "mofa_icp_reject")
+                    on_border = has & (border != 0)
+                else:
+                    on_border = torch.zeros_like(has)
+                keep = has & ~on_border & (weight > 0)
+                w = torch.where(keep, weight, zero)
+                solver.system(verts, moved, res["closest"], None, res["face"], target_verts, TV, target_faces, TF, w, hweight, hpos, metric,
+                              point_weight, alpha)
+                n = (V + ICP_CHUNK - 1) // ICP_CHUNK
+                sums = torch.empty(2, n, 1, dtype=torch.float64, device=dev)
+                for row, src in enumerate((solver.energy, w)):
+                    lib.check(lib.load().mofa_icp_reduce(src.data_ptr(), V, 1, sums[row].data_ptr(), lib.stream()), "mofa_icp_reduce")
+                head = torch.cat([_icp_reduce(sums[0], n, 1), _icp_reduce(sums[1], n, 1),
+                                  torch.stack([keep.sum(), (~finite).sum(), (finite & ~has).sum(), on_border.sum()]).double()])
+                clock = lap("system", clock)
+                x.copy_(d)
+                solver.solve(alpha, x)
+                t = x - d
+                step = torch.sqrt((t[:, 0] * t[:, 0] + t[:, 1] * t[:, 1]) + t[:, 2] * t[:, 2]).max()
+                host = torch.cat([head, step.reshape(1), solver.tail()]).cpu().numpy()       # the one read of this iteration
+                clock = lap("solve", clock)
+                sum_e, sum_w, (n_used, n_bad, n_none, n_border) = float(host[0]), float(host[1]), (int(v) for v in host[2:6])
+                entry = {"stiffness": alpha, "rms": math.sqrt(sum_e / sum_w) if sum_w > 0.0 else float("nan"), "used": n_used,
+                         "rejected": {"non_finite": n_bad, "beyond" if max_distance is not None else "no_face": n_none, "border": n_border},
+                         "cg_steps": 0, "rho": float("nan"), "stop": None, "step": float("nan")}
+                history.append(entry)
+                if n_used == 0:                                  # (the solve that was enqueued is not taken up)
+                    stopped = "no_correspondences"
+                    break
+                rho, steps, stop = solver.record(who, host[7:])
+                entry["cg_steps"], entry["rho"], entry["stop"] = steps, float(rho[-1]), stop
+                if stop == "breakdown" and steps == 0 and rho[0] > 0.0:
+                    stopped = "singular"
+                    break
+                entry["step"] = float(host[6])
+                d, x = x, d
+                done += 1
+                if entry["step"] <= tol * extent:
+                    status = "converged"
+                    break
+            if stopped:
+                status = stopped
+                break
+        _warp_apply(verts, d, V, moved)
+    out = result(moved, history, done, status, b["grid"])
+    if timing:
+        out["times"] = times
+    return out
+
+
 # faces whose clipped box of samples holds at least this many pixels are walked one wavefront per face (mofa_raster_faces); the choice
 # changes no bit of the frame.  profiles/mesh_raster.md holds the sweep it comes from.
 WAVE_MIN_PIXELS = 64
