@@ -736,6 +736,36 @@ int mofa_icp_reject(const int32_t* face, const float* bary, int64_t N, const int
  *                     moved x, _TOL2 = cg_tol * cg_tol, rec[MOFA_WARP_REC_RHO + s] = rho_s for s = 0 .. K.  work holds
  *                     mofa_warp_workspace_doubles(V) doubles (r, z, p, q and the levels of the two sums); bad as mofa_warp_matvec's.
  *                     1 <= cg_iterations <= MOFA_WARP_MAX_CG, 0 <= cg_tol < 1.
+ * As-rigid-as-possible stiffness (mesh.warp(stiffness_model = "arap"), mesh.deform): the stiffness term becomes
+ *     alpha / 2 sum_i sum_{j in N(i)} |(y_i - y_j) - R_i (v_i - v_j)|^2,   y = v + d,   R_i a rotation per vertex,
+ * whose normal equations in d keep the matrix D + alpha L (x) I3 and add alpha g to b.  Both kernels run one thread per vertex i over
+ * nbr[offsets[i] .. offsets[i + 1]) in that order, with v widened to double:  e = v_i - v_j  (per component).
+ *   mofa_warp_rotations  the rotation R [V,9] (double, row-major) that maximises sum_j e' . R e,  e'_c = e_c + (d_i,c - d_j,c), by Horn's
+ *                     quaternion form:
+ *                       S_ab = 0.0;  S_ab += e_a * e'_b   (a, b = x, y, z: nine sums)
+ *                       N_00 = (Sxx + Syy) + Szz;  N_01 = Syz - Szy;  N_02 = Szx - Sxz;  N_03 = Sxy - Syx;
+ *                       N_11 = (Sxx - Syy) - Szz;  N_12 = Sxy + Syx;  N_13 = Szx + Sxz;
+ *                       N_22 = (Syy - Sxx) - Szz;  N_23 = Syz + Szy;  N_33 = (Szz - Sxx) - Syy;   N symmetric,  W = I (4 x 4)
+ *                     then MOFA_WARP_JACOBI_SWEEPS sweeps over the pairs (p, q) = (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); a pair with
+ *                     N_pq == 0 is skipped, otherwise with x = N_pq:
+ *                       theta = (N_qq - N_pp) / (2.0 * x);   t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+ *                       c = 1.0 / sqrt(t * t + 1.0);   s = t * c;
+ *                       N_pp = N_pp - t * x;   N_qq = N_qq + t * x;   N_pq = N_qp = 0.0;
+ *                       k != p, q:      N_kp' = c * N_kp - s * N_kq;   N_kq' = s * N_kp + c * N_kq   (both from the old values; N stays symmetric)
+ *                       k = 0 .. 3:     W_kp' = c * W_kp - s * W_kq;   W_kq' = s * W_kp + c * W_kq
+ *                     Afterwards m = the index of the largest N_mm, the lowest among equal ones (0, then 1, 2, 3 each only when strictly
+ *                     larger), q = column m of W, n = sqrt(((q_0 q_0 + q_1 q_1) + q_2 q_2) + q_3 q_3), (w, x, y, z) = q / n and
+ *                       R = [1 - 2 (yy + zz),  2 (xy - wz),  2 (xz + wy);   2 (xy + wz),  1 - 2 (xx + zz),  2 (yz - wx);
+ *                            2 (xz - wy),  2 (yz + wx),  1 - 2 (xx + yy)]     (products first, e.g. 1.0 - 2.0 * (y * y + z * z))
+ *                     and fit [V] (double):  fit = 0.0;  r_c = e'_c - ((R_c0 e_0 + R_c1 e_1) + R_c2 e_2);  fit += (r_0 r_0 + r_1 r_1) + r_2 r_2.
+ *                     Always a proper rotation, also for a flat (rank 2) neighbourhood; with d = 0, S is symmetric, row 0 of N is never
+ *                     rotated and R is the identity bit for bit (an empty list: S = 0, the identity).  A non-finite entry of S or of R
+ *                     gives R = I, fit = 0 and is counted; a list outside [0, E) or a neighbour outside [0, V) gives R = I, fit = 0 and
+ *                     is counted apart: bad [ceil(V / 256)][2] (int64; written): per workgroup of 256 vertices the index faults, then
+ *                     the non-finite fits.  No NaN leaves the kernel.
+ *   mofa_warp_arap_rhs   b [V,3] (double, in and out):  g_c = 0.0;  Rs = R_i + R_j (entrywise);  t_c = (Rs_c0 e_0 + Rs_c1 e_1) + Rs_c2 e_2;
+ *                     g_c += 0.5 * t_c - e_c;  then  b_c = b_c + alpha * g_c.  All R = I gives g = 0 exactly.  A vertex with a bad list
+ *                     or neighbour leaves its b alone and is counted: bad [ceil(V / 256)] (int64; written).  R != b.
  * A null pointer, a count out of range, an unknown metric, a negative or non-finite alpha / point_weight, the plane metric with both or
  * neither of face / normals, or handle weights without positions returns MOFA_EINVAL with a message. */
 #define MOFA_WARP_MAX_CG 10000
@@ -753,6 +783,11 @@ int mofa_warp_dot(const double* a, const double* b, int64_t V, double* partial, 
 size_t mofa_warp_workspace_doubles(int64_t V);
 int mofa_warp_solve(const double* D, const double* b, const double* minv, const int64_t* offsets, const int32_t* nbr, int64_t E, int64_t V,
                     double alpha, int32_t cg_iterations, double cg_tol, double* x, double* work, double* rec, int64_t* bad, void* stream);
+#define MOFA_WARP_JACOBI_SWEEPS 7 /* 5 bring the off-diagonal norm of N below 2^-50 of its norm on the tests' catalogue; + 2 */
+int mofa_warp_rotations(const float* verts, const double* disp, const int64_t* offsets, const int32_t* nbr, int64_t E, int64_t V, double* R,
+                        double* fit, int64_t* bad, void* stream);
+int mofa_warp_arap_rhs(const float* verts, const double* R, const int64_t* offsets, const int32_t* nbr, int64_t E, int64_t V, double alpha,
+                       double* b, int64_t* bad, void* stream);
 
 /* ---- occupancy-culled rendering: skip the network where an occupancy grid says the space is empty ---------------------------------
  * The grid lives on the lattice of mofa_grid_points (nx x ny x nz samples at lo + (i,j,k) step): (nx-1)(ny-1)(nz-1) cells, one byte

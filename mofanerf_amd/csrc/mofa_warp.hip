@@ -20,6 +20,13 @@
 //            kernel that produces the vectors; upper levels by mofa_icp_reduce)
 //   solve    r = b - A x, z = minv r, p = z;  per step: q = A p, a = rho / (p . q), x += a p, r -= a q, z = minv r, rho' = r . z,
 //            p = z + (rho' / rho) p;  frozen (rho <= tol^2 rho0, or p . q > 0 false): no vector is written any more.
+//
+// The as-rigid-as-possible stiffness (mesh.warp(stiffness_model="arap"), mesh.deform) keeps that matrix and changes the right-hand side:
+//   rotations  S_ab = 0.0 + e_a e'_b over the list (e = v_i - v_j, e' = e + (d_i - d_j));  Horn's symmetric 4 x 4 matrix of S;  its eigenvector
+//              of the largest eigenvalue by MOFA_WARP_JACOBI_SWEEPS cyclic Jacobi sweeps;  R_i the rotation of that unit quaternion;
+//              fit_i = sum_j |e' - R_i e|^2.  A non-finite S or R gives the identity and fit 0, counted.
+//   arap_rhs   g_c = 0.0 + (0.5 ((Rs_c0 e_0 + Rs_c1 e_1) + Rs_c2 e_2) - e_c) over the list with Rs = R_i + R_j;  b_c = b_c + alpha g_c
+// Every index into the two 4 x 4 matrices is a compile-time constant (the pairs are template arguments), so they live in registers.
 #include <math.h>
 
 #include "mofa_common.h"
@@ -317,6 +324,187 @@ __global__ void k_warp_cg_scalar(double* __restrict__ rec, const double* __restr
     rec[MOFA_WARP_REC_A] = 0.0;
 }
 
+// one Jacobi rotation in the plane (P, Q) of the symmetric matrix a (both triangles kept) and of the eigenvector matrix v; the header's order
+template <int P, int Q>
+__device__ __forceinline__ void warp_jacobi_pair(double (&a)[4][4], double (&v)[4][4]) {
+    const double apq = a[P][Q];
+    if (apq != 0.0) {
+        const double theta = (a[Q][Q] - a[P][P]) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0);
+        const double s = t * c;
+        a[P][P] = a[P][P] - t * apq, a[Q][Q] = a[Q][Q] + t * apq;
+        a[P][Q] = 0.0, a[Q][P] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k != P && k != Q) {
+                const double akp = a[k][P], akq = a[k][Q];
+                a[k][P] = a[P][k] = c * akp - s * akq;
+                a[k][Q] = a[Q][k] = s * akp + c * akq;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double vkp = v[k][P], vkq = v[k][Q];
+            v[k][P] = c * vkp - s * vkq;
+            v[k][Q] = s * vkp + c * vkq;
+        }
+    }
+}
+
+// the rotation (row-major) that best takes the rest edges of a neighbourhood onto the deformed ones, from their covariance S (finite);
+// false when an entry of it is not finite
+__device__ __forceinline__ bool warp_fit_rotation(const double (&S)[3][3], double (&R)[9]) {
+    double a[4][4], v[4][4];
+    a[0][0] = (S[0][0] + S[1][1]) + S[2][2], a[0][1] = S[1][2] - S[2][1], a[0][2] = S[2][0] - S[0][2], a[0][3] = S[0][1] - S[1][0];
+    a[1][1] = (S[0][0] - S[1][1]) - S[2][2], a[1][2] = S[0][1] + S[1][0], a[1][3] = S[2][0] + S[0][2];
+    a[2][2] = (S[1][1] - S[0][0]) - S[2][2], a[2][3] = S[1][2] + S[2][1];
+    a[3][3] = (S[2][2] - S[0][0]) - S[1][1];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (q < p) a[p][q] = a[q][p];
+            v[p][q] = p == q ? 1.0 : 0.0;
+        }
+    }
+#pragma unroll 1
+    for (int sweep = 0; sweep < MOFA_WARP_JACOBI_SWEEPS; ++sweep) {      // (rolled: the sweep indexes nothing)
+        warp_jacobi_pair<0, 1>(a, v), warp_jacobi_pair<0, 2>(a, v), warp_jacobi_pair<0, 3>(a, v);
+        warp_jacobi_pair<1, 2>(a, v), warp_jacobi_pair<1, 3>(a, v), warp_jacobi_pair<2, 3>(a, v);
+    }
+    // the column of the largest diagonal entry, the lowest index among equal ones
+    double best = a[0][0], q0 = v[0][0], q1 = v[1][0], q2 = v[2][0], q3 = v[3][0];
+#pragma unroll
+    for (int m = 1; m < 4; ++m) {                                       // (selects of values: a branch here would keep v in memory)
+        const bool larger = a[m][m] > best;
+        const double c0 = v[0][m], c1 = v[1][m], c2 = v[2][m], c3 = v[3][m];
+        best = larger ? a[m][m] : best;
+        q0 = larger ? c0 : q0, q1 = larger ? c1 : q1, q2 = larger ? c2 : q2, q3 = larger ? c3 : q3;
+    }
+    const double n = sqrt(((q0 * q0 + q1 * q1) + q2 * q2) + q3 * q3);
+    const double w = q0 / n, x = q1 / n, y = q2 / n, z = q3 / n;
+    R[0] = 1.0 - 2.0 * (y * y + z * z), R[1] = 2.0 * (x * y - w * z), R[2] = 2.0 * (x * z + w * y);
+    R[3] = 2.0 * (x * y + w * z), R[4] = 1.0 - 2.0 * (x * x + z * z), R[5] = 2.0 * (y * z - w * x);
+    R[6] = 2.0 * (x * z - w * y), R[7] = 2.0 * (y * z + w * x), R[8] = 1.0 - 2.0 * (x * x + y * y);
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) finite &= (bool)isfinite(R[k]);
+    return finite;
+}
+
+__global__ __launch_bounds__(256) void k_warp_rotations(const float* __restrict__ verts, const double* __restrict__ disp, WarpGraph g,
+                                                        double* __restrict__ R, double* __restrict__ fit, int64_t* __restrict__ bad) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    int is_bad = 0, is_odd = 0;
+    if (i < g.V) {
+        double Ri[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+        double f = 0.0;
+        double vi[3], di[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) vi[c] = (double)verts[i * 3 + c], di[c] = disp[i * 3 + c];
+        long long k0, k1;
+        bool ok = warp_list(g, i, k0, k1);
+        double S[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+        if (ok) {
+            for (long long k = k0; k < k1; ++k) {
+                const int j = g.nbr[k];
+                if (!warp_in_range(j, g.V)) {
+                    ok = false;
+                    break;
+                }
+                double e[3], ep[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    e[c] = vi[c] - (double)verts[(long long)j * 3 + c];
+                    ep[c] = e[c] + (di[c] - disp[(long long)j * 3 + c]);
+                }
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+#pragma unroll
+                    for (int b = 0; b < 3; ++b) S[a][b] += e[a] * ep[b];
+                }
+            }
+        }
+        if (!ok) {
+            is_bad = 1;
+        } else {
+            bool finite = true;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+#pragma unroll
+                for (int b = 0; b < 3; ++b) finite &= (bool)isfinite(S[a][b]);
+            }
+            double Rq[9];
+            if (finite) finite = warp_fit_rotation(S, Rq);
+            if (!finite) {
+                is_odd = 1;
+            } else {
+#pragma unroll
+                for (int c = 0; c < 9; ++c) Ri[c] = Rq[c];
+                for (long long k = k0; k < k1; ++k) {
+                    const long long j = g.nbr[k];
+                    double e[3], r[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) e[c] = vi[c] - (double)verts[j * 3 + c];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const double ep = e[c] + (di[c] - disp[j * 3 + c]);
+                        r[c] = ep - ((Ri[3 * c] * e[0] + Ri[3 * c + 1] * e[1]) + Ri[3 * c + 2] * e[2]);
+                    }
+                    f += (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 9; ++c) R[i * 9 + c] = Ri[c];
+        fit[i] = f;
+    }
+    const int n_bad = __syncthreads_count(is_bad);
+    const int n_odd = __syncthreads_count(is_odd);
+    if (threadIdx.x == 0) bad[(long long)blockIdx.x * 2] = n_bad, bad[(long long)blockIdx.x * 2 + 1] = n_odd;
+}
+
+__global__ __launch_bounds__(256) void k_warp_arap_rhs(const float* __restrict__ verts, const double* __restrict__ R, WarpGraph g, double alpha,
+                                                       double* __restrict__ b, int64_t* __restrict__ bad) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    int is_bad = 0;
+    if (i < g.V) {
+        long long k0, k1;
+        bool ok = warp_list(g, i, k0, k1);
+        double gi[3] = {0.0, 0.0, 0.0};
+        if (ok) {
+            double vi[3], Ri[9];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) vi[c] = (double)verts[i * 3 + c];
+#pragma unroll
+            for (int c = 0; c < 9; ++c) Ri[c] = R[i * 9 + c];
+            for (long long k = k0; k < k1; ++k) {
+                const int j = g.nbr[k];
+                if (!warp_in_range(j, g.V)) {
+                    ok = false;
+                    break;
+                }
+                double e[3], Rs[9];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) e[c] = vi[c] - (double)verts[(long long)j * 3 + c];
+#pragma unroll
+                for (int c = 0; c < 9; ++c) Rs[c] = Ri[c] + R[(long long)j * 9 + c];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) gi[c] += 0.5 * ((Rs[3 * c] * e[0] + Rs[3 * c + 1] * e[1]) + Rs[3 * c + 2] * e[2]) - e[c];
+            }
+        }
+        if (ok) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) b[i * 3 + c] = b[i * 3 + c] + alpha * gi[c];
+        } else {
+            is_bad = 1;
+        }
+    }
+    const int n_bad = __syncthreads_count(is_bad);
+    if (threadIdx.x == 0) bad[blockIdx.x] = n_bad;
+}
+
 inline unsigned blocks_of(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // the levels of a sum over V rows: n[0] = ceil(V / 1024) first-level sums, n[l + 1] = ceil(n[l] / 1024) until one is left
@@ -467,6 +655,26 @@ int mofa_warp_solve(const double* D, const double* b, const double* minv, const 
     }
     hipLaunchKernelGGL(k_warp_cg_scalar, dim3(1), dim3(64), 0, s, rec, rz, rz, K, K);
     return check_launch("k_warp_cg_scalar");
+}
+
+int mofa_warp_rotations(const float* verts, const double* disp, const int64_t* offsets, const int32_t* nbr, int64_t E, int64_t V, double* R,
+                        double* fit, int64_t* bad, void* stream) {
+    WarpGraph g;
+    if (int rc = warp_graph("warp_rotations", offsets, nbr, E, V, g)) return rc;
+    MOFA_REQUIRE(verts && disp && R && fit && bad, "warp_rotations: null pointer");
+    hipLaunchKernelGGL(k_warp_rotations, dim3(blocks_of(V, 256)), dim3(256), 0, (hipStream_t)stream, verts, disp, g, R, fit, bad);
+    return check_launch("k_warp_rotations");
+}
+
+int mofa_warp_arap_rhs(const float* verts, const double* R, const int64_t* offsets, const int32_t* nbr, int64_t E, int64_t V, double alpha,
+                       double* b, int64_t* bad, void* stream) {
+    WarpGraph g;
+    if (int rc = warp_graph("warp_arap_rhs", offsets, nbr, E, V, g)) return rc;
+    MOFA_REQUIRE(verts && R && b && bad, "warp_arap_rhs: null pointer");
+    MOFA_REQUIRE(R != b, "warp_arap_rhs: the rotations and the right-hand side are two buffers (R == b)");
+    MOFA_REQUIRE(alpha >= 0.0 && isfinite(alpha), "warp_arap_rhs: alpha = %g (want finite, >= 0)", alpha);
+    hipLaunchKernelGGL(k_warp_arap_rhs, dim3(blocks_of(V, 256)), dim3(256), 0, (hipStream_t)stream, verts, R, g, alpha, b, bad);
+    return check_launch("k_warp_arap_rhs");
 }
 
 }  // extern "C"

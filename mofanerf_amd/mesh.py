@@ -2410,6 +2410,55 @@ class _WarpSolver:
         return tail[WARP_REC_RHO:WARP_REC_RHO + self.K + 1].copy(), int(tail[3]), _WARP_STOPS[int(tail[2])]
 
 
+_WARP_MODELS = ("displacement", "arap")
+
+
+class _WarpArap:
+    """The buffers of the as-rigid-as-possible stiffness, allocated once per call of warp / deform: the rotations fitted to the
+    current d (``R [V,9]`` float64), those of the last iteration taken (``taken``), the per-vertex fit and the two kernels' counters."""
+
+    def __init__(self, V, graph, dev):
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.V, (self.offsets, self.nbr, self.E) = V, graph
+        self.R, self.fit = torch.empty(V, 9, **f64), torch.empty(V, **f64)
+        self.taken = torch.eye(3, **f64).reshape(1, 9).repeat(V, 1)
+        self.sums = torch.empty((V + ICP_CHUNK - 1) // ICP_CHUNK, 1, **f64)
+        self.bad_fit = torch.zeros((V + 255) // 256, 2, dtype=torch.int64, device=dev)
+        self.bad_rhs = torch.zeros((V + 255) // 256, dtype=torch.int64, device=dev)
+
+    def _graph(self):
+        return self.offsets.data_ptr(), self.nbr.data_ptr() if self.E else None, self.E, self.V
+
+    def rotations(self, verts, d):
+        """Fits ``R`` to the displacement ``d`` (``mofa_warp_rotations``); returns the sum of the fit, one number still on the device."""
+        L = lib.load()
+        lib.check(L.mofa_warp_rotations(lib.ptr(verts), d.data_ptr(), *self._graph(), self.R.data_ptr(), self.fit.data_ptr(),
+                                        self.bad_fit.data_ptr(), lib.stream()), "mofa_warp_rotations")
+        lib.check(L.mofa_icp_reduce(self.fit.data_ptr(), self.V, 1, self.sums.data_ptr(), lib.stream()), "mofa_icp_reduce")
+        return _icp_reduce(self.sums, int(self.sums.shape[0]), 1)
+
+    def amend(self, verts, alpha, b):
+        """b += alpha g(R) (``mofa_warp_arap_rhs``)."""
+        lib.check(lib.load().mofa_warp_arap_rhs(lib.ptr(verts), self.R.data_ptr(), *self._graph(), alpha, b.data_ptr(), self.bad_rhs.data_ptr(),
+                                                lib.stream()), "mofa_warp_arap_rhs")
+
+    def tail(self, fit_sum):
+        """What the host reads of an iteration, still on the device: the sum of the fit, the index faults, the non-finite fits."""
+        return torch.cat([fit_sum.reshape(1), torch.stack([self.bad_fit[:, 0].sum() + self.bad_rhs.sum(), self.bad_fit[:, 1].sum()]).double()])
+
+    def energy(self, who, tail):
+        """``arap_energy`` from the host copy of :meth:`tail`."""
+        if int(tail[1]):
+            raise lib.MofaError(f"{who}: {int(tail[1])} indices were out of range inside the rotation fit (the mesh changed while it was warped?)")
+        return 0.5 * float(tail[0])
+
+    def take(self):
+        self.R, self.taken = self.taken, self.R
+
+    def result(self):
+        return self.taken.reshape(self.V, 3, 3)
+
+
 def warp_to(verts: torch.Tensor, faces: torch.Tensor, targets: torch.Tensor, weight: Optional[torch.Tensor] = None,
             normals: Optional[torch.Tensor] = None, metric: str = "point", stiffness: float = 1.0, point_weight: float = 1e-2, init=None,
             cg_iterations: int = 200, cg_tol: float = 1e-8):
@@ -2501,7 +2550,7 @@ def _warp_handles(who, handles, V, dev):
 def warp(verts: torch.Tensor, faces: torch.Tensor, target_verts: torch.Tensor, target_faces: torch.Tensor, metric: str = "plane",
          stiffness=(10.0, 1.0, 0.1), iterations: int = 5, point_weight: float = 1e-2, weight: Optional[torch.Tensor] = None, handles=None,
          max_distance=None, reject_border: bool = True, init=None, tol: float = 0.0, cg_iterations: int = 200, cg_tol: float = 1e-8, grid=None,
-         timing: bool = False) -> dict:
+         timing: bool = False, stiffness_model: str = "displacement") -> dict:
     """Warps the template ``(verts [V,3] float32, faces [F,3] int32)`` onto the target mesh ``(target_verts, target_faces)`` without touching
     its topology — non-rigid registration by stiffness-regularised iterated closest points with one translation per vertex (Amberg-style
     optimal-step N-ICP) —, so that meshes of different triangulations come out in ONE vertex numbering.  The unknown is a
@@ -2530,13 +2579,24 @@ def warp(verts: torch.Tensor, faces: torch.Tensor, target_verts: torch.Tensor, t
     ``p . A p > 0`` false with ``rho_0 > 0``; the last d is kept) or ``"empty"`` (``V == 0``: no launch) —, ``grid`` and, with
     ``timing=True``, ``times``: seconds of ``bin`` and, summed over the iterations, ``query`` (steps 1 - 2), ``system`` (3 - 4) and ``solve``,
     each ended by a device synchronisation.  Every sum has a fixed order and no transcendental is involved: the same input gives the same
-    bytes.  A local method with no per-vertex rotation, no normal-compatibility test and no colour term.
+    bytes.  A local method with no normal-compatibility test and no colour term.
 
-    Raises ``MofaError`` for the scalar arguments :func:`warp_to` refuses, an empty schedule, ``iterations`` outside 0 .. 10000, ``tol`` < 0
+    ``stiffness_model="arap"`` replaces the stiffness term by the as-rigid-as-possible one,
+    ``alpha / 2 sum_i sum_{j in N(i)} |(y_i - y_j) - R_i (v_i - v_j)|^2`` with a rotation ``R_i`` per vertex: between steps 4 and 5 the rotations
+    are fitted to the current d (``mofa_warp_rotations``: Horn's quaternion by a fixed number of Jacobi sweeps, always a proper rotation,
+    the identity bit for bit at d = 0) and the right-hand side is amended (``mofa_warp_arap_rhs``); the matrix and the solve stay the same.
+    A rotation of the template is then free and its edge lengths are kept.  Every history entry gains ``arap_energy`` (the term without
+    alpha, at the d the iteration started from), the result ``rotations [V,3,3] float64`` (those of the last iteration taken; the identity
+    before one) and ``times`` the key ``arap``.  Uniform edge weights only (no cotangent weights), a surface term (no volumetric rigidity),
+    still a local method.  The default ``"displacement"`` runs exactly the launches described above and returns exactly those keys.
+
+    Raises ``MofaError`` for an unknown ``stiffness_model``, the scalar arguments :func:`warp_to` refuses, an empty schedule, ``iterations`` outside 0 .. 10000, ``tol`` < 0
     (before any tensor is looked at), CPU tensors, wrong dtypes or shapes, face or handle indices outside the mesh, a non-finite template
     vertex that a face references, a non-finite target vertex or handle, negative weights, ``max_distance`` not > 0 and a grid out of
     range."""
     who = "warp"
+    if stiffness_model not in _WARP_MODELS:
+        raise lib.MofaError(f"{who}: stiffness_model = {stiffness_model!r} (want 'displacement' or 'arap')")
     levels, point_weight, cg_tol = _warp_args(who, metric, stiffness, point_weight, cg_iterations, cg_tol)
     iterations, tol = _icp_args(who, "rigid", metric, iterations, tol)
     maxd = _max_distance(who, max_distance)
@@ -2548,12 +2608,19 @@ def warp(verts: torch.Tensor, faces: torch.Tensor, target_verts: torch.Tensor, t
     weight = _icp_weight(who, weight, V, dev)
     hweight, hpos = _warp_handles(who, handles, V, dev)
 
+    arap = None
+
     def result(moved, history, done, status, g):
-        return {"verts": moved, "displacement": d, "history": history, "iterations": done, "status": status, "grid": g}
+        out = {"verts": moved, "displacement": d, "history": history, "iterations": done, "status": status, "grid": g}
+        if stiffness_model == "arap":
+            out["rotations"] = arap.result() if arap is not None else torch.zeros(0, 3, 3, dtype=torch.float64, device=dev)
+        return out
 
     if V == 0:
         return result(verts.clone(), [], 0, "empty", grid if grid is not None else (1, 1, 1))
     history, status, done, times = [], "iterations", 0, dict.fromkeys(("bin", "query", "system", "solve"), 0.0)
+    if stiffness_model == "arap":
+        times["arap"] = 0.0
 
     def lap(name, since):
         if timing:
@@ -2563,6 +2630,8 @@ def warp(verts: torch.Tensor, faces: torch.Tensor, target_verts: torch.Tensor, t
 
     with torch.cuda.device(dev):
         moved = torch.empty_like(verts)
+        if stiffness_model == "arap":
+            arap = _WarpArap(V, _warp_graph(adj, V, dev), dev)
         if TV == 0 or TF == 0:
             return result(_warp_apply(verts, d, V, moved), [], 0, "no_correspondences", grid if grid is not None else (1, 1, 1))
         clock = lap("bin", 0.0)
@@ -2603,17 +2672,27 @@ def warp(verts: torch.Tensor, faces: torch.Tensor, target_verts: torch.Tensor, t
                 head = torch.cat([_icp_reduce(sums[0], n, 1), _icp_reduce(sums[1], n, 1),
                                   torch.stack([keep.sum(), (~finite).sum(), (finite & ~has).sum(), on_border.sum()]).double()])
                 clock = lap("system", clock)
+                if arap is not None:
+                    fit_sum = arap.rotations(verts, d)
+                    arap.amend(verts, alpha, solver.b)
+                    clock = lap("arap", clock)
                 x.copy_(d)
                 solver.solve(alpha, x)
                 t = x - d
                 step = torch.sqrt((t[:, 0] * t[:, 0] + t[:, 1] * t[:, 1]) + t[:, 2] * t[:, 2]).max()
-                host = torch.cat([head, step.reshape(1), solver.tail()]).cpu().numpy()       # the one read of this iteration
+                if arap is None:
+                    host = torch.cat([head, step.reshape(1), solver.tail()]).cpu().numpy()       # the one read of this iteration
+                else:
+                    host = torch.cat([head, step.reshape(1), solver.tail(), arap.tail(fit_sum)]).cpu().numpy()
+                    host, fitted = host[:-3], host[-3:]
                 clock = lap("solve", clock)
                 sum_e, sum_w, (n_used, n_bad, n_none, n_border) = float(host[0]), float(host[1]), (int(v) for v in host[2:6])
                 entry = {"stiffness": alpha, "rms": math.sqrt(sum_e / sum_w) if sum_w > 0.0 else float("nan"), "used": n_used,
                          "rejected": {"non_finite": n_bad, "beyond" if max_distance is not None else "no_face": n_none, "border": n_border},
                          "cg_steps": 0, "rho": float("nan"), "stop": None, "step": float("nan")}
                 history.append(entry)
+                if arap is not None:
+                    entry["arap_energy"] = arap.energy(who, fitted)
                 if n_used == 0:                                  # (the solve that was enqueued is not taken up)
                     stopped = "no_correspondences"
                     break
@@ -2625,6 +2704,8 @@ def warp(verts: torch.Tensor, faces: torch.Tensor, target_verts: torch.Tensor, t
                 entry["step"] = float(host[6])
                 d, x = x, d
                 done += 1
+                if arap is not None:
+                    arap.take()
                 if entry["step"] <= tol * extent:
                     status = "converged"
                     break
@@ -2636,6 +2717,86 @@ def warp(verts: torch.Tensor, faces: torch.Tensor, target_verts: torch.Tensor, t
     if timing:
         out["times"] = times
     return out
+
+
+def deform(verts: torch.Tensor, faces: torch.Tensor, handles, stiffness: float = 1.0, iterations: int = 40, init=None, tol: float = 0.0,
+           cg_iterations: int = 200, cg_tol: float = 1e-8) -> dict:
+    """Edits the mesh ``(verts [V,3] float32, faces [F,3] int32)`` by its handles — as-rigid-as-possible deformation (Sorkine and Alexa's
+    local/global iteration): ``handles = (index [K], position [K,3] float32, weight)`` as in :func:`warp` pull landmark
+    vertices to positions and the surface follows as rigidly as it can.  The unknown is a displacement ``d [V,3] float64`` that minimises
+
+        ``stiffness / 2 sum_i sum_{j in N(i)} |(y_i - y_j) - R_i (v_i - v_j)|^2  +  sum_l beta_l |y_l - p_l|^2``,   ``y = v + d``,
+
+    over d and one rotation ``R_i`` per vertex, on :func:`vertex_adjacency`'s lists with uniform edge weights.  ``iterations`` times: the
+    rotations are fitted to the current d (``mofa_warp_rotations``: Horn's quaternion of the neighbourhood's covariance by a fixed number
+    of Jacobi sweeps — always a proper rotation, also on a flat neighbourhood, and the identity bit for bit at d = 0); the system is built
+    with the handles as the only data term (``mofa_warp_system``, every data weight 0), the rotation term is added to its right-hand side
+    (``mofa_warp_arap_rhs``) and it is solved from the current d by the conjugate gradients of :func:`warp` (``mofa_warp_solve``); the host
+    reads one small record per iteration.  ``init`` (a displacement [V,3] float64) starts the iteration elsewhere than at rest; it stops
+    early when ``max_i |delta d_i| <= tol * extent`` (the largest edge of the vertices' box).
+
+    Returns a dict: ``verts [V,3] float32 = (float)(verts + d)``, ``displacement [V,3] float64``, ``rotations [V,3,3] float64`` (those the
+    last solve taken was built from; the identity before one), ``history`` (per iteration: ``arap_energy`` — the stiffness term without
+    ``stiffness`` at the d the iteration started from, with its freshly fitted rotations —, ``cg_steps``, ``rho``, ``stop``, ``step``),
+    ``iterations`` (solves taken) and ``status``: ``"iterations"``, ``"converged"``, ``"singular"`` (as in :func:`warp`) or ``"empty"``
+    (``V == 0``: no launch).  Every sum has a fixed order: the same input gives the same bytes.
+
+    What is fixed and what is not claimed: uniform edge weights only, no cotangent weights, so an irregular triangulation is stiffer where
+    it is denser; a surface term, no volumetric or tetrahedral rigidity; a local method — it finds the rest-like pose near its start, not
+    the global minimum; and local/global converges linearly, slowly when the handles are few: on the tests' 9 x 9 patch, 32 border handles
+    reach 1e-5 of a rigid motion by 60 degrees in 40 iterations, five handles are still 6e-2 away after 40 and 1.6e-3 after 160 (a NumPy
+    prototype; README).  A vertex without neighbours and without a handle keeps its start.  ``faces`` and the numbering are never touched.
+
+    Raises ``MofaError`` for the scalar arguments :func:`warp_to` refuses (one stiffness), ``iterations`` outside 0 .. 10000, ``tol`` < 0
+    (before any tensor is looked at), missing handles or handles without a positive weight, CPU tensors, wrong dtypes or shapes, face or
+    handle indices outside the mesh and a non-finite vertex that a face references."""
+    who = "deform"
+    levels, _, cg_tol = _warp_args(who, "point", stiffness, 0.0, cg_iterations, cg_tol)
+    if len(levels) != 1:
+        raise lib.MofaError(f"{who}: stiffness = {stiffness!r} (want one value)")
+    iterations, tol = _icp_args(who, "rigid", "point", iterations, tol)
+    if handles is None:
+        raise lib.MofaError(f"{who}: handles = (index [K], position [K,3], weight) are required: they are the only data term")
+    alpha = levels[0]
+    V, F, dev, adj, d = _warp_template(who, verts, faces, init)
+    hweight, hpos = _warp_handles(who, handles, V, dev)
+    if V == 0:
+        return {"verts": verts.clone(), "displacement": d, "rotations": torch.zeros(0, 3, 3, dtype=torch.float64, device=dev), "history": [],
+                "iterations": 0, "status": "empty"}
+    with torch.cuda.device(dev):
+        if not bool((hweight > 0).any()):
+            raise lib.MofaError(f"{who}: no handle has a positive weight")
+        _, extent = _icp_extent(torch.stack([verts.min(0).values, verts.max(0).values]).cpu().numpy())
+        graph = _warp_graph(adj, V, dev)
+        solver, arap = _WarpSolver(V, graph, int(cg_iterations), cg_tol, dev), _WarpArap(V, graph, dev)
+        zero = torch.zeros(V, dtype=torch.float64, device=dev)
+        x, moved = torch.empty_like(d), torch.empty_like(verts)
+        history, status, done = [], "iterations", 0
+        for _ in range(iterations):
+            fit_sum = arap.rotations(verts, d)
+            solver.system(verts, verts, verts, None, None, None, 0, None, 0, zero, hweight, hpos, "point", 0.0, alpha)
+            arap.amend(verts, alpha, solver.b)
+            x.copy_(d)
+            solver.solve(alpha, x)
+            t = x - d
+            step = torch.sqrt((t[:, 0] * t[:, 0] + t[:, 1] * t[:, 1]) + t[:, 2] * t[:, 2]).max()
+            host = torch.cat([step.reshape(1), solver.tail(), arap.tail(fit_sum)]).cpu().numpy()       # the one read of this iteration
+            entry = {"arap_energy": arap.energy(who, host[-3:]), "cg_steps": 0, "rho": float("nan"), "stop": None, "step": float("nan")}
+            history.append(entry)
+            rho, steps, stop = solver.record(who, host[1:-3])
+            entry["cg_steps"], entry["rho"], entry["stop"] = steps, float(rho[-1]), stop
+            if stop == "breakdown" and steps == 0 and rho[0] > 0.0:
+                status = "singular"
+                break
+            entry["step"] = float(host[0])
+            d, x = x, d
+            done += 1
+            arap.take()
+            if entry["step"] <= tol * extent:
+                status = "converged"
+                break
+        _warp_apply(verts, d, V, moved)
+    return {"verts": moved, "displacement": d, "rotations": arap.result(), "history": history, "iterations": done, "status": status}
 
 
 # faces whose clipped box of samples holds at least this many pixels are walked one wavefront per face (mofa_raster_faces); the choice
