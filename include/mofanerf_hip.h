@@ -789,6 +789,41 @@ int mofa_warp_rotations(const float* verts, const double* disp, const int64_t* o
 int mofa_warp_arap_rhs(const float* verts, const double* R, const int64_t* offsets, const int32_t* nbr, int64_t E, int64_t V, double alpha,
                        double* b, int64_t* bad, void* stream);
 
+/* Linear shape models: the device side of mesh.shape_model / shape_synthesize / shape_project / shape_fit (mesh.py drives them; the
+ * M x M eigen-decomposition and the K x K solves run on the host).  No atomics of any kind and a fixed summation order that does not depend
+ * on the launch geometry or on how the pairs are tiled: the same input gives the same bytes every time.  No kernel waits on another
+ * thread.  All arithmetic is fp64 (fp32 inputs widened first), every operation rounded separately (no FMA, no matrix instruction).
+ *   mofa_shape_gram      P [R, N] (double, row-major), 1 <= R <= MOFA_SHAPE_MAX_ROWS;  weight [N / group] (double) or NULL;  group 1 or 3.
+ *                        partial [ceil(N / MOFA_ICP_CHUNK), R (R + 1) / 2] (double): pair (a, b), a <= b, sits at a R - a (a - 1) / 2 + (b - a)
+ *                        (the upper triangle row by row).  Column j of pair (a, b) has the term
+ *                          term_j = weight[j / group] * (P[a][j] * P[b][j])        (weight NULL:  term_j = P[a][j] * P[b][j])
+ *                        and a column whose weight is not `> 0` adds nothing, whatever P holds there (NaN, inf).  Chunk k holds the columns
+ *                        [1024 k, min(1024 (k + 1), N)): thread t of its 256 starts at 0.0 and adds the terms of the chunk's columns t,
+ *                        t + 256, t + 512, t + 768 (those below N) in that order; then `for w = 128, 64, .. 1: p[t] += p[t + w] for t < w`
+ *                        over the 256 partial sums, and p[0] is the chunk's number: mofa_icp_reduce's sum of the [N, R (R + 1) / 2] matrix
+ *                        of the terms, without that matrix.  The caller reduces the chunk rows with mofa_shape_reduce until one is left.
+ *   mofa_shape_reduce    mofa_icp_reduce for rows of any width: out [ceil(M / MOFA_ICP_CHUNK), ncols] from in [M, ncols] (double),
+ *                        1 <= ncols <= 32,896, the same additions in the same order.  in != out.
+ *   mofa_shape_centre    meshes [M, n] (float), 1 <= M <= MOFA_SHAPE_MAX_ROWS:  s = 0.0;  s += (double)meshes[m][j]  (m ascending);
+ *                        mean[j] = s / (double)M;   X[m][j] = (double)meshes[m][j] - mean[j].   mean [n], X [M, n] (double).
+ *   mofa_shape_combine   out [B, n] (double) from coef [B, R] and rows [R, n] (double):  acc = 0.0;  acc += coef[b][r] * rows[r][j]
+ *                        (r ascending);  out[b][j] = base[j] + acc  (base [n] double), or acc with base NULL.  1 <= B <= 65,535.
+ *   mofa_shape_plane_rows   P [K + 1, V] (double) for the model's vertices i (moved [V,3], their closest points closest [V,3], both float,
+ *                        face [V] int32 on the target mesh verts [TV,3] / faces [TF,3]):  n = the unit normal of faces[face[i]] exactly as
+ *                        mofa_icp_terms takes it;  with transform = [s, R (row-major 3 x 3), t] (13 doubles, HOST; t unused)
+ *                          q_c = s * ((R[0][c] * n_x + R[1][c] * n_y) + R[2][c] * n_z)     (s R^T n: the normal in the model's frame)
+ *                          P[k][i] = (q_x * m_x + q_y * m_y) + q_z * m_z,   m = modes[k][i]   (modes [K, V, 3] double;  0 <= K < 256)
+ *                          P[K][i] = (n_x * d_x + n_y * d_y) + n_z * d_z,   d = (double)moved[i] - (double)closest[i]
+ *                        A face or vertex index outside the mesh writes NaN into column i of all K + 1 rows (the caller gives it weight 0).
+ * A null pointer or a count out of range returns MOFA_EINVAL with a message. */
+#define MOFA_SHAPE_MAX_ROWS 256
+int mofa_shape_gram(const double* P, int32_t R, int64_t N, const double* weight, int32_t group, double* partial, void* stream);
+int mofa_shape_reduce(const double* in, int64_t M, int64_t ncols, double* out, void* stream);
+int mofa_shape_centre(const float* meshes, int32_t M, int64_t n, double* mean, double* X, void* stream);
+int mofa_shape_combine(const double* base, const double* coef, const double* rows, int32_t B, int32_t R, int64_t n, double* out, void* stream);
+int mofa_shape_plane_rows(const float* moved, const float* closest, const int32_t* face, const float* verts, int64_t TV, const int32_t* faces,
+                          int64_t TF, const double transform[13], const double* modes, int32_t K, int64_t V, double* P, void* stream);
+
 /* ---- occupancy-culled rendering: skip the network where an occupancy grid says the space is empty ---------------------------------
  * The grid lives on the lattice of mofa_grid_points (nx x ny x nz samples at lo + (i,j,k) step): (nx-1)(ny-1)(nz-1) cells, one byte
  * each (0 / 1), cell index (i (ny-1) + j) (nz-1) + k.  The lattice needs 2 <= n < 2^24 per axis and fewer than 2^31 cells.

@@ -127,6 +127,11 @@ SIGNATURES = {
     "mofa_warp_solve": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i64, _i64, C.c_double, _i32, C.c_double, _fp, _fp, _fp, _fp, _fp]),
     "mofa_warp_rotations": (C.c_int, [_fp, _fp, _fp, _fp, _i64, _i64, _fp, _fp, _fp, _fp]),
     "mofa_warp_arap_rhs": (C.c_int, [_fp, _fp, _fp, _fp, _i64, _i64, C.c_double, _fp, _fp, _fp]),
+    "mofa_shape_gram": (C.c_int, [_fp, _i32, _i64, _fp, _i32, _fp, _fp]),
+    "mofa_shape_reduce": (C.c_int, [_fp, _i64, _i64, _fp, _fp]),
+    "mofa_shape_centre": (C.c_int, [_fp, _i32, _i64, _fp, _fp, _fp]),
+    "mofa_shape_combine": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i64, _fp, _fp]),
+    "mofa_shape_plane_rows": (C.c_int, [_fp, _fp, _fp, _fp, _i64, _fp, _i64, _d3, _fp, _i32, _i64, _fp, _fp]),
     "mofa_occ_workspace_bytes": (_sz, [_i64]),
     "mofa_occ_cells": (C.c_int, [_fp, _i64, _i64, _i64, C.c_float, _i32, _fp, _fp]),
     "mofa_occ_dilate": (C.c_int, [_fp, _i64, _i64, _i64, _i32, _fp, _fp, _fp]),

@@ -13,6 +13,8 @@ density normals (``refine_vertices``, ``density_normals``, ``mofa_edge_*`` / ``m
 volume and march its zero level: a mesh with no density level to choose (``mofa_tsdf_*``).
 ``register`` / ``register_meshes`` bring points or a mesh into another mesh's frame by rigid or similarity ICP over ``closest_points``' grid,
 ``fit_transform`` does it for explicit correspondences and ``transform_points`` applies the result (``mofa_icp_*``).
+``shape_model`` builds a linear shape model (mean, modes, standard deviations) of meshes with one vertex numbering, ``shape_synthesize`` /
+``shape_project`` evaluate and invert it, ``shape_fit`` fits it to a mesh with a triangulation of its own (``mofa_shape_*``).
 
 ``Renderer.query_density`` and ``Renderer.extract_mesh`` are the user-facing entry points; this module holds the pieces they share.
 The mesh is watertight and consistently oriented (normals toward lower density); vertices and faces come out in a fixed order with
@@ -2797,6 +2799,563 @@ def deform(verts: torch.Tensor, faces: torch.Tensor, handles, stiffness: float =
                 break
         _warp_apply(verts, d, V, moved)
     return {"verts": moved, "displacement": d, "rotations": arap.result(), "history": history, "iterations": done, "status": status}
+
+
+SHAPE_MAX_ROWS = 256          # MOFA_SHAPE_MAX_ROWS: meshes of a model, and modes + 1 of a fit
+SHAPE_PIVOT_FLOOR = 2.0 ** -40   # a Cholesky pivot at or below this share of its diagonal entry has lost 40 bits to cancellation: singular
+SHAPE_JACOBI_SWEEPS = 64      # the cap of the host's cyclic Jacobi (8 meshes take 5 sweeps, 256 random ones 11)
+
+
+# ---- the host side of a shape model: plain IEEE fp64 (+ - * / sqrt), every operation in the order DESIGN 3.25 writes down -----------------
+def _shape_jacobi(G):
+    """(eigenvalues [n] descending, eigenvectors [n,n] in columns, sweeps) of the symmetric ``G`` by cyclic Jacobi.  A sweep visits the pairs
+    (p, q), p < q, row by row: (0,1) (0,2) .. (0,n-1) (1,2) ..  With x = A_pq: a pair with x == 0 is skipped; one with
+    ``|A_pp| + 100 |x| == |A_pp|`` and ``|A_qq| + 100 |x| == |A_qq|``, or with ``norm + |x| == norm`` (norm = the largest ``|G_ii|``: G's own
+    entries carry a larger error, and without this rule the null space of a rank-deficient G is turned for many sweeps), gets A_pq = A_qp = 0
+    and is skipped; otherwise
+    ``theta = (A_qq - A_pp) / (2 x)``, ``t = (theta >= 0 ? 1 : -1) / (|theta| + sqrt(theta theta + 1))``, ``c = 1 / sqrt(t t + 1)``, ``s = t c``;
+    columns p, q of A become ``c a_p - s a_q`` and ``s a_p + c a_q`` (both from the old columns), rows p, q the same vectors, ``A_pp = A_pp -
+    t x``, ``A_qq = A_qq + t x``, ``A_pq = A_qp = 0``; columns p, q of W (the identity at first) turn the same way.  The loop stops after a
+    sweep that rotated nothing, or after SHAPE_JACOBI_SWEEPS.  The diagonal is sorted descending, equal values by their index; every
+    eigenvector's component of largest magnitude (the first among equal ones) is made positive."""
+    A = np.array(G, dtype=np.float64)
+    n = len(A)
+    W = np.eye(n)
+    norm = float(np.abs(np.diag(A)).max()) if n else 0.0
+    sweeps = 0
+    with np.errstate(all="ignore"):
+        for _ in range(SHAPE_JACOBI_SWEEPS):
+            rotated = 0
+            for p in range(n - 1):
+                for q in range(p + 1, n):
+                    x = float(A[p, q])
+                    if x == 0.0:
+                        continue
+                    g = 100.0 * abs(x)
+                    if (abs(A[p, p]) + g == abs(A[p, p]) and abs(A[q, q]) + g == abs(A[q, q])) or norm + abs(x) == norm:
+                        A[p, q] = A[q, p] = 0.0
+                        continue
+                    theta = (float(A[q, q]) - float(A[p, p])) / (2.0 * x)
+                    t = (1.0 if theta >= 0 else -1.0) / (abs(theta) + math.sqrt(theta * theta + 1.0))
+                    c = 1.0 / math.sqrt(t * t + 1.0)
+                    s = t * c
+                    cp, cq = A[:, p].copy(), A[:, q].copy()
+                    npp, nqq = cp[p] - t * x, cq[q] + t * x
+                    new_p, new_q = c * cp - s * cq, s * cp + c * cq
+                    A[:, p], A[:, q] = new_p, new_q
+                    A[p, :], A[q, :] = new_p, new_q
+                    A[p, p], A[q, q] = npp, nqq
+                    A[p, q] = A[q, p] = 0.0
+                    wp, wq = W[:, p].copy(), W[:, q].copy()
+                    W[:, p], W[:, q] = c * wp - s * wq, s * wp + c * wq
+                    rotated += 1
+            sweeps += 1
+            if rotated == 0:
+                break
+    lam = np.diag(A).copy()
+    order = sorted(range(n), key=lambda i: (-lam[i], i))
+    lam, W = lam[order], W[:, order]
+    for k in range(n):
+        if W[int(np.argmax(np.abs(W[:, k]))), k] < 0:
+            W[:, k] = -W[:, k]
+    return lam, W, sweeps
+
+
+def _shape_solve(A, rhs, lam):
+    """x of ``(A + lam I) x = rhs`` by :func:`_icp_solve`'s Cholesky (L's columns left to right, every sum over k ascending; a column's
+    elements are updated together, elementwise); None when a pivot is not above SHAPE_PIVOT_FLOOR times its diagonal entry (two equal
+    modes leave a pivot of rounding noise, of either sign) and finite, or the solution is not finite."""
+    H = np.array(A, dtype=np.float64)
+    n = len(rhs)
+    for i in range(n):
+        H[i, i] = H[i, i] + lam
+    Lm = np.zeros((n, n))
+    with np.errstate(all="ignore"):
+        for j in range(n):
+            col = H[j:, j].copy()
+            for k in range(j):
+                col = col - Lm[j:, k] * Lm[j, k]
+            s = float(col[0])
+            if not (s > SHAPE_PIVOT_FLOOR * float(H[j, j]) and math.isfinite(s)):
+                return None
+            d = math.sqrt(s)
+            Lm[j, j] = d
+            Lm[j + 1:, j] = col[1:] / d
+        r = np.array(rhs, dtype=np.float64)
+        z = np.zeros(n)
+        for i in range(n):
+            z[i] = r[i] / Lm[i, i]
+            r[i + 1:] = r[i + 1:] - Lm[i + 1:, i] * z[i]
+        Lt, x = Lm.tolist(), [0.0] * n
+        for i in range(n - 1, -1, -1):
+            s = float(z[i])
+            for k in range(i + 1, n):
+                s = s - Lt[k][i] * x[k]
+            x[i] = s / Lt[i][i]
+    x = np.array(x, dtype=np.float64)
+    return x if np.isfinite(x).all() else None
+
+
+def _shape_matrix(sums, R):
+    """The symmetric [R,R] matrix of the R (R + 1) / 2 sums of mofa_shape_gram (the upper triangle row by row)."""
+    G = np.zeros((R, R))
+    iu = np.triu_indices(R)
+    G[iu] = sums
+    G.T[iu] = sums
+    return G
+
+
+def _shape_step(sums, K, c, lam):
+    """(the step of ``(A + lam I) dc = -(g + lam c)`` or None, the energy) from the sums of the modes and the residual row."""
+    G = _shape_matrix(sums, K + 1)
+    g = G[:K, K].copy()
+    rhs = -g if lam == 0.0 else -(g + lam * np.asarray(c, dtype=np.float64))
+    return _shape_solve(G[:K, :K], rhs, lam), float(G[K, K])
+
+
+def _shape_inverse(state):
+    """``[1 / s, R^T, -(1 / s) R^T t]`` (13 doubles) of the pose (s, q, t)."""
+    s, q, t = state
+    R = _quat_rotation(q)
+    si = 1.0 / s
+    return (C.c_double * 13)(si, R[0], R[3], R[6], R[1], R[4], R[7], R[2], R[5], R[8],
+                             *[-(si * ((R[r] * t[0] + R[3 + r] * t[1]) + R[6 + r] * t[2])) for r in range(3)])
+
+
+# ---- the device side ----------------------------------------------------------------------------------------------------------------------
+def _shape_gram(P, R, N, weight=None, group=1):
+    """The R (R + 1) / 2 sums of mofa_shape_gram over ``P [R, N]`` (float64, GPU), reduced level by level; on the host."""
+    L, dev = lib.load(), P.device
+    npairs, M = R * (R + 1) // 2, (N + ICP_CHUNK - 1) // ICP_CHUNK
+    rows = torch.empty(M, npairs, dtype=torch.float64, device=dev)
+    lib.check(L.mofa_shape_gram(P.data_ptr(), R, N, None if weight is None else weight.data_ptr(), group, rows.data_ptr(), lib.stream()),
+              "mofa_shape_gram")
+    while M > 1:
+        n = (M + ICP_CHUNK - 1) // ICP_CHUNK
+        out = torch.empty(n, npairs, dtype=torch.float64, device=dev)
+        lib.check(L.mofa_shape_reduce(rows.data_ptr(), M, npairs, out.data_ptr(), lib.stream()), "mofa_shape_reduce")
+        rows, M = out, n
+    return rows.reshape(-1).cpu().numpy()
+
+
+def _shape_combine(base, coef, rows, n):
+    """``out [B, n]`` (float64, GPU) of mofa_shape_combine: ``coef [B, R]`` (host), ``rows [R, n]``, ``base [n]`` or None."""
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    B, R = coef.shape
+    out = torch.empty(B, n, dtype=torch.float64, device=rows.device)
+    c = torch.from_numpy(coef).to(rows.device)
+    lib.check(lib.load().mofa_shape_combine(None if base is None else base.data_ptr(), c.data_ptr(), rows.data_ptr(), B, R, n, out.data_ptr(),
+                                            lib.stream()), "mofa_shape_combine")
+    return out
+
+
+def _shape_model_arg(who, model, components=None):
+    """(mean [V,3], modes [K',V,3], V, K', device) of a model dict, checked; K' = min(components, K)."""
+    try:
+        mean, modes = model["mean"], model["modes"]
+    except (KeyError, TypeError):
+        raise lib.MofaError(f"{who}: want a model dict of shape_model / read_shape_model (mean, modes)")
+    for name, t in (("mean", mean), ("modes", modes)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise lib.MofaError(f"{who}: the HIP path needs the model on the GPU (got a CPU {name}); there is no CPU fallback")
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise lib.MofaError(f"{who}: want a contiguous float64 {name}, got {t.dtype} contiguous={t.is_contiguous()}")
+    if mean.dim() != 2 or mean.shape[1] != 3 or modes.dim() != 3 or modes.shape[1:] != mean.shape or modes.device != mean.device:
+        raise lib.MofaError(f"{who}: want mean [V,3] and modes [K,V,3] on one device, got {tuple(mean.shape)} and {tuple(modes.shape)}")
+    K, V = int(modes.shape[0]), int(mean.shape[0])
+    if K >= SHAPE_MAX_ROWS or V > INT32_MAX // 3:
+        raise lib.MofaError(f"{who}: {K} modes (want < {SHAPE_MAX_ROWS}) / {V} vertices (want 3 V < 2^31)")
+    if components is not None:
+        if isinstance(components, (bool, np.bool_)) or not isinstance(components, (int, np.integer)) or int(components) < 0:
+            raise lib.MofaError(f"{who}: components = {components!r} (want an integer >= 0, or None)")
+        K = min(K, int(components))
+    return mean, modes[:K], V, K, mean.device
+
+
+def _shape_regularize(who, regularize) -> float:
+    lam = float(regularize)
+    if not (lam >= 0.0 and math.isfinite(lam)):
+        raise lib.MofaError(f"{who}: regularize = {regularize} (want finite and >= 0)")
+    return lam
+
+
+def _shape_coeffs(who, coeffs, K):
+    """Coefficients from the caller as a host array [B, K'] with K' <= K."""
+    try:
+        c = np.asarray(_host(coeffs), dtype=np.float64)
+        c = c.reshape(1, -1) if c.ndim == 1 else c
+        if c.ndim != 2 or c.shape[1] > K or not np.isfinite(c).all():
+            raise ValueError(f"shape {c.shape}")
+    except (TypeError, ValueError) as e:
+        raise lib.MofaError(f"{who}: want finite coefficients [B, K'] with K' <= {K}: {e}")
+    return np.ascontiguousarray(c)
+
+
+def _shape_synth(mean, modes, V, c):
+    """``mean + sum_k c[b][k] modes[k]`` as [B, V, 3] float64 (mofa_shape_combine); no mode: the mean."""
+    c = np.asarray(c, dtype=np.float64).reshape(len(c), -1)
+    if c.shape[1] == 0 or V == 0:
+        return mean.unsqueeze(0).repeat(len(c), 1, 1)
+    return _shape_combine(mean, c, modes[:c.shape[1]], 3 * V).reshape(len(c), V, 3)
+
+
+def shape_model(meshes: torch.Tensor, components=None, rank_tol: float = 1e-10, align: Optional[str] = None, align_iterations: int = 2,
+                timing: bool = False) -> dict:
+    """A linear shape model — a mean and modes of variation — of ``meshes [M,V,3] float32`` on the GPU, ``2 <= M <= 256`` meshes with one
+    vertex numbering (outputs of :func:`warp`): principal components by the M x M Gram matrix, the covariance itself is never formed.
+
+    1. ``mofa_shape_centre``: ``mean[j]`` = the sum over the meshes in their order divided by M, ``X[m] = meshes[m] - mean`` (float64),
+    2. ``mofa_shape_gram``: ``G = X X^T`` in a fixed order (chunks of 1,024 columns, ``mofa_icp_reduce``'s sum; ``mofa_shape_reduce`` for
+       the later levels),
+    3. the host decomposes G by cyclic Jacobi written with ``+ - * / sqrt`` only (:func:`_shape_jacobi` states the order of the pairs, the
+       rotation, the skip rule, the stopping rule, the order of the eigenvalues and the sign rule),
+    4. K = ``components``, or the number of eigenvalues above ``rank_tol`` times the largest; at most M - 1, and only eigenvalues > 0,
+    5. ``sigma_k = sqrt(lambda_k / (M - 1))``,
+    6. ``modes[k] = (sigma_k / sqrt(lambda_k)) * sum_m U[m][k] X[m]`` (``mofa_shape_combine``, m ascending): a mode is in length units,
+       a coefficient in standard deviations.
+
+    ``align="rigid"`` / ``"similarity"`` first runs ``align_iterations`` rounds, each fitting every mesh onto the current mean (rounded to
+    float32) by :func:`fit_transform` (all vertices, the point metric, from the round before) and taking the mean of the moved meshes;
+    ``transforms [M,4,4]`` (NumPy) then holds what moved each mesh.  Returns a dict: ``mean [V,3]``, ``modes [K,V,3]`` (float64, GPU),
+    ``sigma [K]``, ``eigenvalues [M]``, ``coeffs [M,K]`` (the training meshes' own coefficients, ``U[m][k] * (sqrt(lambda_k) / sigma_k)``),
+    ``explained [K]`` (``lambda_k`` over the sum of all in their order) — NumPy float64 —, ``n_meshes`` and ``status``: ``"ok"``, or
+    ``"sweeps"`` when the Jacobi ran into its cap.  The same input gives the same bytes.  ``timing=True`` adds ``times``: seconds of ``align``,
+    ``gram`` (centre, Gram kernel, reduce levels and the read-back), ``jacobi`` (the host decomposition) and ``modes``, each ended by a device
+    synchronisation.
+
+    Raises ``MofaError`` for CPU tensors, wrong dtypes or shapes, M < 2, M > 256, V = 0, non-finite vertices and an unknown ``align``."""
+    who = "shape_model"
+    lib.ptr(meshes)
+    if meshes.dim() != 3 or meshes.shape[2] != 3:
+        raise lib.MofaError(f"{who}: want meshes [M,V,3], got {tuple(meshes.shape)}")
+    M, V, dev = int(meshes.shape[0]), int(meshes.shape[1]), meshes.device
+    if not 2 <= M <= SHAPE_MAX_ROWS:
+        raise lib.MofaError(f"{who}: {M} meshes (want 2 .. {SHAPE_MAX_ROWS})")
+    if not 1 <= V <= INT32_MAX // 3:
+        raise lib.MofaError(f"{who}: {V} vertices (want 1 .. (2^31 - 1) / 3)")
+    if align not in (None, "rigid", "similarity"):
+        raise lib.MofaError(f"{who}: align = {align!r} (want None, 'rigid' or 'similarity')")
+    if components is not None and (isinstance(components, (bool, np.bool_)) or not isinstance(components, (int, np.integer)) or int(components) < 0):
+        raise lib.MofaError(f"{who}: components = {components!r} (want an integer >= 0, or None)")
+    if isinstance(align_iterations, (bool, np.bool_)) or not isinstance(align_iterations, (int, np.integer)) or not 0 <= int(align_iterations) <= 100:
+        raise lib.MofaError(f"{who}: align_iterations = {align_iterations!r} (want an integer 0 .. 100)")
+    rank_tol = float(rank_tol)
+    if not 0.0 <= rank_tol < 1.0:
+        raise lib.MofaError(f"{who}: rank_tol = {rank_tol} (want in [0, 1))")
+    n, L = 3 * V, lib.load()
+    times = dict.fromkeys(("align", "gram", "jacobi", "modes"), 0.0)
+
+    def lap(name, since):
+        if timing:
+            torch.cuda.synchronize(dev)
+            times[name] += time.perf_counter() - since
+        return time.perf_counter()
+
+    with torch.cuda.device(dev):
+        if not bool(torch.isfinite(meshes).all()):
+            raise lib.MofaError(f"{who}: the meshes hold non-finite vertices")
+        clock = time.perf_counter()
+        mean = torch.empty(V, 3, dtype=torch.float64, device=dev)
+        X = torch.empty(M, n, dtype=torch.float64, device=dev)
+
+        def centre(ms):
+            lib.check(L.mofa_shape_centre(lib.ptr(ms), M, n, mean.data_ptr(), X.data_ptr(), lib.stream()), "mofa_shape_centre")
+
+        transforms = None
+        if align is not None:
+            src, fits = meshes, [None] * M
+            for _ in range(int(align_iterations)):
+                centre(meshes)
+                mean32 = mean.to(torch.float32)
+                fits = [fit_transform(src[m], mean32, model=align, metric="point", init=fits[m]) for m in range(M)]
+                meshes = torch.stack([f["moved"] for f in fits]).contiguous()
+            transforms = np.stack([f["matrix"] if f is not None else np.eye(4) for f in fits])
+        clock = lap("align", clock)
+        centre(meshes)
+        G = _shape_matrix(_shape_gram(X, M, n), M)
+        clock = lap("gram", clock)
+        lam, U, sweeps = _shape_jacobi(G)
+        clock = lap("jacobi", clock)
+        K = int(components) if components is not None else int((lam > rank_tol * float(lam.max())).sum())
+        K = min(K, M - 1)
+        pos = 0
+        while pos < K and lam[pos] > 0:
+            pos += 1
+        K = pos
+        sigma = np.array([math.sqrt(lam[k] / float(M - 1)) for k in range(K)])
+        root = np.array([math.sqrt(lam[k]) for k in range(K)])
+        if K:
+            modes = torch.from_numpy(sigma / root).to(dev)[:, None] * _shape_combine(None, U[:, :K].T.copy(), X, n)
+        else:
+            modes = torch.zeros(0, n, dtype=torch.float64, device=dev)
+        clock = lap("modes", clock)
+    total = 0.0
+    for v in lam:
+        total = total + float(v)
+    out = {"mean": mean, "modes": modes.reshape(K, V, 3).contiguous(), "sigma": sigma, "eigenvalues": lam, "coeffs": U[:, :K] * (root / sigma)[None, :],
+           "explained": lam[:K] / total if K else np.zeros(0), "n_meshes": M, "status": "ok" if sweeps < SHAPE_JACOBI_SWEEPS else "sweeps"}
+    if transforms is not None:
+        out["transforms"] = transforms
+    if timing:
+        out["times"] = times
+    return out
+
+
+def shape_synthesize(model: dict, coeffs, dtype=torch.float64) -> torch.Tensor:
+    """The meshes ``mean + sum_k coeffs[b][k] modes[k]`` of a model of :func:`shape_model`: ``coeffs [B, K']`` (a host array or a tensor;
+    ``K' <= K``: the leading modes) gives ``[B,V,3]`` on the model's device (``mofa_shape_combine``: the sum over k ascending from 0.0,
+    then added to the mean, in float64).  ``dtype=torch.float32`` rounds that result once at the end.  Raises ``MofaError`` for a model
+    that is not on the GPU, coefficients that are not finite or too many, and another dtype."""
+    who = "shape_synthesize"
+    mean, modes, V, K, dev = _shape_model_arg(who, model)
+    if dtype not in (torch.float64, torch.float32):
+        raise lib.MofaError(f"{who}: dtype = {dtype} (want torch.float64 or torch.float32)")
+    c = _shape_coeffs(who, coeffs, K)
+    if len(c) == 0:
+        return torch.empty(0, V, 3, dtype=dtype, device=dev)
+    if len(c) > 65535:
+        raise lib.MofaError(f"{who}: {len(c)} meshes in one call (want <= 65,535)")
+    with torch.cuda.device(dev):
+        return _shape_synth(mean, modes, V, c).to(dtype)
+
+
+def shape_project(model: dict, verts: torch.Tensor, weight: Optional[torch.Tensor] = None, regularize: float = 0.0, components=None) -> dict:
+    """The coefficients of a mesh with the model's vertex numbering (``verts [V,3] float32``: an output of :func:`warp`, or landmarks with
+    ``weight [V] float64`` 0 elsewhere): the minimum of ``sum_i w_i |mean_i + sum_k c_k m_ki - v_i|^2 + regularize |c|^2``.  The residual
+    ``mean - v`` joins the modes as one more row; one pass of ``mofa_shape_gram`` (group 3: a weight per vertex) yields A, g and the
+    energy, and the host solves ``(A + regularize I) c = -g`` by Cholesky.  A vertex that is not finite gets weight 0.  ``components``:
+    the leading modes only.  Returns ``coeffs [K]`` (NumPy float64), ``verts [V,3]`` (float64, GPU: the reconstruction), ``rms`` (weighted,
+    of the reconstruction against ``verts``) and ``status``: ``"ok"``, ``"singular"`` (a pivot of the Cholesky factor is not positive: the
+    weighted vertices do not fix the modes; coefficients 0) or ``"empty"`` (no vertex with a weight > 0)."""
+    who = "shape_project"
+    mean, modes, V, K, dev = _shape_model_arg(who, model, components)
+    if _query_points(who, verts, dev) != V:
+        raise lib.MofaError(f"{who}: the model has {V} vertices, verts {verts.shape[0]}")
+    lam = _shape_regularize(who, regularize)
+    weight = _icp_weight(who, weight, V, dev)
+    c = np.zeros(K)
+    with torch.cuda.device(dev):
+        w = torch.where(torch.isfinite(verts).all(1), weight, torch.zeros_like(weight)) if V else weight
+        if V == 0 or int((w > 0).sum()) == 0:
+            return {"coeffs": c, "verts": _shape_synth(mean, modes, V, c[None])[0], "rms": float("nan"), "status": "empty"}
+        n = 3 * V
+        P = torch.empty(K + 1, n, dtype=torch.float64, device=dev)
+        P[:K] = modes.reshape(K, n)
+        P[K] = (mean - verts.double()).reshape(n)
+        wsum = float(_icp_reduce(w.reshape(V, 1), V, 1).cpu()[0])
+        x, _ = _shape_step(_shape_gram(P, K + 1, n, w, 3), K, c, lam)
+        status = "ok"
+        if x is None:
+            x, status = c, "singular"
+        recon = _shape_synth(mean, modes, V, x[None])[0]
+        e = _shape_gram((recon - verts.double()).reshape(1, n).contiguous(), 1, n, w, 3)[0]
+        with np.errstate(all="ignore"):
+            rms = float(np.sqrt(e / np.float64(wsum)))
+    return {"coeffs": x, "verts": recon, "rms": rms, "status": status}
+
+
+def shape_fit(model: dict, target_verts: torch.Tensor, target_faces: torch.Tensor, metric: str = "plane", pose: Optional[str] = None,
+              iterations: int = 20, regularize: float = 0.0, init=None, init_coeffs=None, weight: Optional[torch.Tensor] = None,
+              max_distance=None, reject_border: bool = True, tol: float = 0.0, components=None, grid=None, timing: bool = False) -> dict:
+    """Fits a model of :func:`shape_model` to the mesh ``(target_verts [T,3] float32, target_faces [F,3] int32)`` with a triangulation of
+    its own, by iterated closest points: the unknowns are the coefficients ``c`` and, with ``pose`` (one of :func:`register`'s models), a
+    pose ``x -> s R x + t`` — K + 7 numbers, between :func:`register` (7) and :func:`warp` (3 V).  The fit cannot leave the span of the
+    examples, which is what keeps it steady on partial or noisy targets; its ``verts`` are :func:`warp`'s natural ``init``.  The target is
+    binned once (``grid`` as in :func:`closest_points`: it changes no bit).  An iteration is
+
+    * with ``pose``, the pose phase: synthesise the model (``mofa_shape_combine``), round it to float32 and move it
+      (``mofa_icp_apply``), find the closest points, reject exactly as :func:`register` does (not finite, no face / beyond
+      ``max_distance``, on the target's border with ``reject_border``) and take one step of :func:`register` on (s, R, t) — its sums, its
+      solve, its pivot (the centre of the target's box) and extent;
+    * the shape phase: synthesise, move, query and reject again, then one Gauss–Newton step ``(A + regularize I) dc = -(g + regularize c)``
+      from one pass of ``mofa_shape_gram`` over K + 1 rows.  ``metric="plane"``: ``mofa_shape_plane_rows`` gives ``s (R^T n) . m_ki`` per mode
+      and the residual ``n . (moved - closest)`` along the closest face's normal n (group 1).  ``"point"``: the closest points are taken
+      back into the model's frame by ``mofa_icp_apply`` with the inverse pose (composed on the host: ``1 / s``, ``R^T``, ``-(1 / s) R^T t``),
+      the rows are the modes and the residual ``y - c'`` (group 3).  A column whose residual is not finite gets weight 0.
+
+    ``plane`` is the default because a model vertex may slide along the target's surface at no cost: where the target is the model's
+    own surface the first step lands on it (the test scene: 5e-9 after one iteration), while ``point`` pulls every vertex to a closest
+    point that is the wrong partner until the shapes agree, and contracts by a constant factor (there 0.6 per iteration).  ``weight [V]
+    float64`` (>= 0), ``init`` (a pose as :func:`register` takes it), ``init_coeffs [K]``, ``components`` (the leading modes only).  The
+    fit has converged when the pose step and ``max |dc|`` are both ``<= tol``.
+
+    Returns a dict: ``coeffs [K]``, ``scale``, ``rotation [3,3]``, ``translation [3]``, ``matrix [4,4]`` (NumPy float64), ``verts [V,3]
+    float32`` (in the target's frame), ``model_verts [V,3]`` float64 (in the model's), ``history`` (per iteration ``{"pose": entry or None,
+    "shape": entry}``, an entry holding ``used``, ``rejected`` by cause, ``rms`` and ``step``), ``iterations``, ``grid`` and ``status``:
+    ``"converged"``, ``"iterations"``, ``"singular"`` (a Cholesky pivot of either step is not positive; the last state is kept),
+    ``"no_correspondences"`` (also a target without faces) or ``"empty"`` (a model without vertices).  ``timing=True`` adds ``times``:
+    seconds of ``bin`` and, summed over the iterations, ``query`` (synthesis, move, closest points), ``rows`` (rejection, pose sums, rows),
+    ``gram`` and ``host``, each ended by a device synchronisation.  No robust kernel and no coarse-to-fine: a local method.
+
+    Raises ``MofaError`` for CPU tensors, wrong dtypes or shapes, a face index outside the target, a non-finite target vertex, negative
+    weights, ``max_distance`` not > 0, ``regularize`` < 0, an unknown metric or pose model and a grid out of range."""
+    who = "shape_fit"
+    mean, modes, V, K, dev = _shape_model_arg(who, model, components)
+    TV, F, tdev = _mesh_tensors(who, target_verts, target_faces)
+    if tdev != dev:
+        raise lib.MofaError(f"{who}: the model on {dev}, the target on {tdev}")
+    iterations, tol = _icp_args(who, pose if pose is not None else "rigid", metric, iterations, tol)
+    lam = _shape_regularize(who, regularize)
+    maxd = _max_distance(who, max_distance)
+    grid = _dist_grid_arg(who, grid)
+    weight = _icp_weight(who, weight, V, dev)
+    state = _icp_init(who, init)
+    c = np.zeros(K) if init_coeffs is None else _shape_coeffs(who, init_coeffs, SHAPE_MAX_ROWS)[0][:K].copy()
+    if len(c) != K:
+        raise lib.MofaError(f"{who}: init_coeffs holds {len(c)} coefficients, the fit has {K} modes")
+    times = dict.fromkeys(("bin", "query", "rows", "gram", "host"), 0.0)
+    L = lib.load()
+
+    def lap(name, since):
+        if timing:
+            torch.cuda.synchronize(dev)
+            times[name] += time.perf_counter() - since
+        return time.perf_counter()
+
+    def finish(history, done, status, grid_used):
+        with torch.cuda.device(dev):
+            y = _shape_synth(mean, modes, V, c[None])[0]
+            moved = _icp_apply(y.to(torch.float32), V, state) if V else torch.empty(0, 3, dtype=torch.float32, device=dev)
+        out = _icp_result(state, moved, history, done, status)
+        out["verts"] = out.pop("moved")
+        out["coeffs"], out["model_verts"], out["grid"] = c, y, grid_used
+        if timing:
+            out["times"] = times
+        return out
+
+    if V == 0:
+        return finish([], 0, "empty", grid)
+    if TV == 0 or F == 0:
+        return finish([], 0, "no_correspondences", grid)
+    history, status, done = [], "iterations", 0
+    n = 3 * V
+    with torch.cuda.device(dev):
+        clock = time.perf_counter()
+        b = _dist_lists(who, target_verts, target_faces, TV, F, grid)
+        mu, extent = _icp_extent(b["box"])
+        if reject_border:
+            face_border, vert_border = _border_flags(who, target_faces, TV, F)
+            border = torch.empty(V, dtype=torch.uint8, device=dev)
+        zero = torch.zeros_like(weight)
+        moved = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        P = torch.empty(K + 1, n if metric == "point" else V, dtype=torch.float64, device=dev)
+        if metric == "point":
+            P[:K] = modes.reshape(K, n)
+        clock = lap("bin", clock)
+
+        def correspond():
+            y = _shape_synth(mean, modes, V, c[None])[0]
+            _icp_apply(y.to(torch.float32), V, state, moved)
+            res = _dist_query(moved, V, target_verts, target_faces, TV, F, b, maxd)
+            nonlocal clock
+            clock = lap("query", clock)
+            finite = torch.isfinite(moved).all(1) & (torch.isfinite(res["d2"]) | (res["face"] < 0))
+            has = finite & (res["face"] >= 0)
+            if reject_border:
+                lib.check(L.mofa_icp_reject(res["face"].data_ptr(), lib.ptr(res["bary"]), V, target_faces.data_ptr(), F, TV, face_border.data_ptr(),
+                                            vert_border.data_ptr(), border.data_ptr(), lib.stream()), "mofa_icp_reject")
+                on_border = has & (border != 0)
+            else:
+                on_border = torch.zeros_like(has)
+            keep = has & ~on_border & (weight > 0)
+            n_used, n_bad, n_none, n_border = (int(v) for v in torch.stack([keep.sum(), (~finite).sum(), (finite & ~has).sum(), on_border.sum()]).cpu())
+            entry = {"used": n_used, "rejected": {"non_finite": n_bad, "beyond" if max_distance is not None else "no_face": n_none,
+                                                  "border": n_border}}
+            return y, res, keep, entry
+
+        for _ in range(iterations):
+            record = {"pose": None, "shape": None}
+            history.append(record)
+            pose_step = 0.0
+            if pose is not None:
+                y, res, keep, entry = correspond()
+                record["pose"] = entry
+                w = torch.where(keep, weight, zero)
+                sums = _icp_sums(moved, res["closest"], None, res["face"], target_verts, TV, target_faces, F, w, V, mu, metric)
+                clock = lap("rows", clock)
+                new, stop = _icp_update(state, sums, _ICP_MODEL[pose], mu, extent, entry)
+                clock = lap("host", clock)
+                if stop:
+                    status = stop
+                    break
+                state, pose_step = new, entry["step"]
+            y, res, keep, entry = correspond()
+            record["shape"] = entry
+            entry["rms"], entry["step"] = float("nan"), float("nan")
+            if metric == "plane":
+                T = (C.c_double * 13)(state[0], *_quat_rotation(state[1]), *state[2])
+                lib.check(L.mofa_shape_plane_rows(lib.ptr(moved), lib.ptr(res["closest"]), res["face"].data_ptr(), lib.ptr(target_verts), TV,
+                                                  target_faces.data_ptr(), F, T, modes.data_ptr() if K else None, K, V, P.data_ptr(), lib.stream()),
+                          "mofa_shape_plane_rows")
+                keep = keep & torch.isfinite(P[K])
+                group, width = 1, V
+            else:
+                back = torch.empty_like(moved)
+                lib.check(L.mofa_icp_apply(lib.ptr(res["closest"]), V, _shape_inverse(state), lib.ptr(back), lib.stream()), "mofa_icp_apply")
+                P[K] = (y - back.double()).reshape(n)
+                keep = keep & torch.isfinite(P[K].reshape(V, 3)).all(1)
+                group, width = 3, n
+            w = torch.where(keep, weight, zero)
+            entry["used"] = int(keep.sum())
+            wsum = float(_icp_reduce(w.reshape(V, 1), V, 1).cpu()[0])
+            clock = lap("rows", clock)
+            sums = _shape_gram(P, K + 1, width, w, group)
+            clock = lap("gram", clock)
+            with np.errstate(all="ignore"):
+                entry["rms"] = float(np.sqrt(sums[-1] / np.float64(wsum))) if wsum > 0 else float("nan")
+            if entry["used"] == 0:
+                status = "no_correspondences"
+                break
+            dc, _ = _shape_step(sums, K, c, lam)
+            clock = lap("host", clock)
+            if dc is None:
+                status = "singular"
+                break
+            c = c + dc
+            entry["step"] = float(np.abs(dc).max()) if K else 0.0
+            done += 1
+            if pose_step <= tol and entry["step"] <= tol:
+                status = "converged"
+                break
+    return finish(history, done, status, b["grid"])
+
+
+def write_shape_model(path: str, model: dict, faces=None) -> None:
+    """Writes a model of :func:`shape_model` (and, with ``faces [F,3]``, the triangles its vertices share) as one ``.npz`` of plain arrays:
+    ``mean``, ``modes``, ``sigma``, ``eigenvalues``, ``coeffs``, ``explained`` (float64), ``n_meshes``, ``transforms`` if the model has them,
+    ``faces`` (int32).  Nothing is pickled."""
+    arrays = {k: np.asarray(_host(model[k]), dtype=np.float64) for k in ("mean", "modes", "sigma", "eigenvalues", "coeffs", "explained")}
+    arrays["n_meshes"] = np.asarray(int(model["n_meshes"]), dtype=np.int64)
+    if "transforms" in model:
+        arrays["transforms"] = np.asarray(model["transforms"], dtype=np.float64)
+    if faces is not None:
+        arrays["faces"] = np.asarray(_host(faces), dtype=np.int32).reshape(-1, 3)
+    with open(path, "wb") as fh:
+        np.savez(fh, **arrays)
+
+
+def read_shape_model(path: str, device="cuda") -> dict:
+    """The model :func:`write_shape_model` wrote (``allow_pickle=False``): ``mean`` and ``modes`` as float64 tensors on ``device``, the rest
+    NumPy; ``faces`` (an int32 tensor on ``device``) when the file holds them.  ``status`` is ``"ok"``.  Raises ``MofaError`` for a file that
+    is not such a model."""
+    who = "read_shape_model"
+    try:
+        with np.load(path, allow_pickle=False) as z:
+            arrays = {k: z[k] for k in z.files}
+        out = {k: np.asarray(arrays[k], dtype=np.float64) for k in ("sigma", "eigenvalues", "coeffs", "explained")}
+        mean, modes = np.asarray(arrays["mean"], dtype=np.float64), np.asarray(arrays["modes"], dtype=np.float64)
+        out["n_meshes"] = int(arrays["n_meshes"])
+    except (KeyError, ValueError, OSError) as e:
+        raise lib.MofaError(f"{who}: {path} is no shape model: {e}")
+    if mean.ndim != 2 or mean.shape[1] != 3 or modes.ndim != 3 or modes.shape[1:] != mean.shape or len(out["sigma"]) != len(modes):
+        raise lib.MofaError(f"{who}: {path}: mean {mean.shape}, modes {modes.shape}, sigma {out['sigma'].shape} do not belong together")
+    out["mean"], out["modes"] = torch.from_numpy(mean).to(device).contiguous(), torch.from_numpy(modes).to(device).contiguous()
+    if "transforms" in arrays:
+        out["transforms"] = np.asarray(arrays["transforms"], dtype=np.float64)
+    if "faces" in arrays:
+        out["faces"] = torch.from_numpy(np.asarray(arrays["faces"], dtype=np.int32)).to(device).contiguous()
+    out["status"] = "ok"
+    return out
 
 
 # faces whose clipped box of samples holds at least this many pixels are walked one wavefront per face (mofa_raster_faces); the choice
