@@ -603,6 +603,55 @@ int mofa_tsdf_integrate(int64_t nx, int64_t ny, int64_t nz, const float lo[3], c
 int mofa_tsdf_field(int64_t nx, int64_t ny, int64_t nz, const double* acc, const double* wsum, const int32_t* behind, int32_t unobserved,
                     int32_t close_border, float* field, void* workspace, int64_t* counts, void* stream);
 
+/* Multi-view colour baking: posed colour frames projected onto the vertices of a mesh with any triangulation (verts [V,3] float, 1 <= V <=
+ * 2^31 - 1), occlusion-aware through one depth frame per view in the encoding of mofa_tsdf_integrate (the RAY PARAMETER of get_rays; +infinity
+ * background; NaN, -infinity and values <= 0 unknown), and the vertex colours made from what was gathered (mesh.py drives the passes:
+ * mesh.bake_state / bake_integrate / bake_colors / fill_colors).  One thread per vertex, no atomics: the same frames in the same order give the
+ * same bytes, and the views [a | b] in two calls give the bytes of one call with a + b.  All arithmetic is fp64 on the fp32 inputs widened,
+ * every operation rounded separately (no FMA).  1 <= C <= 16 channels.
+ *   the state            per vertex csum [V,C] (double: the weighted colour sum), wsum [V] (double: the weight sum), wbest [V] (double: the
+ *                        largest weight so far), cbest [V,C] (float: the colour of the view with the largest weight so far), seen [V] (int32:
+ *                        the views that entered), occluded [V] (int32: the views in which the vertex failed the depth test) and grazing [V]
+ *                        (int32: the views the angle test rejected); seven DEVICE arrays, zeroed by the caller before the first frame.
+ *   mofa_bake_integrate  normals [V,3] (float, DEVICE) or NULL, images [n_views,H,W,C] and depth [n_views,H,W] (float, DEVICE), cams
+ *                        [n_cams,16] exactly as mofa_tsdf_integrate (n_cams = 1 or n_views).  For the vertex x and every view in order:
+ *                          d[a] = x[a] - c[a][3];  p[a] = (d0 c[0][a] + d1 c[1][a]) + d2 c[2][a];  t = -p[2];  not t > 0: skipped
+ *                          u = cx + fx (p0 / t), v = cy - fy (p1 / t);  u0 = floor(u), v0 = floor(v);  unless 0 <= u0, u0 + 1 <= W - 1,
+ *                          0 <= v0 and v0 + 1 <= H - 1 (tested on the doubles: a non-finite value fails; only then are integer offsets
+ *                          formed, so every load is in bounds): skipped
+ *                          D_k = depth[view] at (v0, u0), (v0, u0 + 1), (v0 + 1, u0), (v0 + 1, u0 + 1):  any D_k unknown or background:
+ *                          skipped (the silhouette erodes);  any t - D_k > depth_tol: occluded += 1, skipped (so do occlusion boundaries)
+ *                          with normals n:  e = -d;  cosv = ((n0 e0 + n1 e1) + n2 e2) / sqrt((e0 e0 + e1 e1) + e2 e2);  not cosv > cos_min:
+ *                          grazing += 1, skipped;  w = 1.0, then `power` times w = w cosv (no pow);  without normals w = 1
+ *                          fu = u - u0, fv = v - v0;  per channel, with c00, c10, c01, c11 the texels at the four corners in the order
+ *                          above:  a = c00 + fu (c10 - c00), b = c01 + fu (c11 - c01), col = a + fv (b - a);  any of the 4 C texels not
+ *                          finite: skipped
+ *                          csum = csum + w col, wsum = wsum + w, seen += 1;  w > wbest (strict: the earlier view keeps a tie): wbest = w,
+ *                          cbest = (float)col
+ *   mofa_bake_resolve    colors [V,C] (float) and valid [V] (uint8): blend MOFA_BAKE_MEAN: (float)(csum / wsum) where wsum > 0;
+ *                        MOFA_BAKE_BEST: cbest where seen > 0; everywhere else `fill` and valid = 0.  counts[MOFA_BAKE_COUNTS] (int64,
+ *                        DEVICE, written, not added to): the coloured vertices, the uncoloured ones with occluded > 0, the uncoloured ones
+ *                        with grazing > 0 only, and the uncoloured ones no view held in a footprint with a known surface (the four classes
+ *                        partition the vertices), by per-block sums in `workspace` (DEVICE, 16 ((V + 255) / 256) bytes) and one
+ *                        fixed-order pass over them.
+ *   mofa_bake_fill       one Jacobi step of hole filling over mesh.vertex_adjacency's lists (offsets [V + 1] int64, nbr [E] int32, 0 <= E
+ *                        <= 2^31 - 1), double-buffered (input and output must differ): an invalid vertex with k >= 1 valid neighbours takes
+ *                        (float)(s / k) per channel, s = 0.0 then s = s + (double)colors_in[j] over its valid neighbours j in list order,
+ *                        and valid_out = 1; every other vertex is copied.  A list that leaves [0, E) or a neighbour outside [0, V) is not
+ *                        dereferenced.
+ * A null pointer, V or C out of range, H or W < 2 or H W >= 2^31, n_views < 1, n_cams other than 1 or n_views, a depth_tol that is not finite
+ * and >= 0, cos_min outside [0, 1), power outside 0 .. 8 or an unknown blend returns MOFA_EINVAL with a message. */
+enum { MOFA_BAKE_COLORED = 0, MOFA_BAKE_OCCLUDED = 1, MOFA_BAKE_GRAZING = 2, MOFA_BAKE_UNSEEN = 3, MOFA_BAKE_COUNTS = 4 };
+enum { MOFA_BAKE_MEAN = 0, MOFA_BAKE_BEST = 1 };
+int mofa_bake_integrate(const float* verts, const float* normals, int64_t V, const float* images, const float* depth, int64_t n_views, int32_t H,
+                        int32_t W, int32_t C, const float* cams, int64_t n_cams, double depth_tol, double cos_min, int32_t power, double* csum,
+                        double* wsum, double* wbest, float* cbest, int32_t* seen, int32_t* occluded, int32_t* grazing, void* stream);
+int mofa_bake_resolve(int64_t V, int32_t C, const double* csum, const double* wsum, const float* cbest, const int32_t* seen,
+                      const int32_t* occluded, const int32_t* grazing, int32_t blend, float fill, float* colors, uint8_t* valid, void* workspace,
+                      int64_t* counts, void* stream);
+int mofa_bake_fill(const float* colors_in, const uint8_t* valid_in, int64_t V, int32_t C, const int64_t* offsets, const int32_t* nbr, int64_t E,
+                   float* colors_out, uint8_t* valid_out, void* stream);
+
 /* Mesh smoothing: Taubin lambda | mu filtering of the vertices of a triangle mesh (verts [V,3] float, faces [F,3] int32) over a fixed-order
  * vertex adjacency (mesh.py drives the passes: mesh.vertex_adjacency, mesh.smooth; 1 <= V, F, E <= 2^31 - 1).  No float or double atomics and
  * a fixed summation order: the same input gives the same bytes every time; the only atomics are the integer counters

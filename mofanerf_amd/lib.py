@@ -110,6 +110,10 @@ SIGNATURES = {
     "mofa_tsdf_integrate": (C.c_int, [_i64, _i64, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_double, _fp, _fp, _i64, _i32, _i32, _fp, _i64,
                                       _i32, _fp, _fp, _fp, _fp, _fp]),
     "mofa_tsdf_field": (C.c_int, [_i64, _i64, _i64, _fp, _fp, _fp, _i32, _i32, _fp, _fp, _fp, _fp]),
+    "mofa_bake_integrate": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _i64, _i32, _i32, _i32, _fp, _i64, C.c_double, C.c_double, _i32, _fp, _fp, _fp, _fp,
+                                      _fp, _fp, _fp, _fp]),
+    "mofa_bake_resolve": (C.c_int, [_i64, _i32, _fp, _fp, _fp, _fp, _fp, _fp, _i32, C.c_float, _fp, _fp, _fp, _fp, _fp]),
+    "mofa_bake_fill": (C.c_int, [_fp, _fp, _i64, _i32, _fp, _fp, _i64, _fp, _fp, _fp]),
     "mofa_smooth_corner_cots": (C.c_int, [_fp, _fp, _i64, _i64, _fp, _fp, _fp]),
     "mofa_smooth_edge_weights": (C.c_int, [_fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp]),
     "mofa_smooth_step": (C.c_int, [_fp, _i64, _fp, _fp, _i64, _fp, _fp, C.c_double, _fp, _fp, _fp]),

@@ -15,6 +15,8 @@ volume and march its zero level: a mesh with no density level to choose (``mofa_
 ``fit_transform`` does it for explicit correspondences and ``transform_points`` applies the result (``mofa_icp_*``).
 ``shape_model`` builds a linear shape model (mean, modes, standard deviations) of meshes with one vertex numbering, ``shape_synthesize`` /
 ``shape_project`` evaluate and invert it, ``shape_fit`` fits it to a mesh with a triangulation of its own (``mofa_shape_*``).
+``bake_state`` / ``bake_integrate`` / ``bake_colors`` project posed colour frames onto a mesh's vertices, occlusion-aware through a depth
+frame per view, and ``fill_colors`` closes the holes over the vertex adjacency (``mofa_bake_*``).
 
 ``Renderer.query_density`` and ``Renderer.extract_mesh`` are the user-facing entry points; this module holds the pieces they share.
 The mesh is watertight and consistently oriented (normals toward lower density); vertices and faces come out in a fixed order with
@@ -1670,6 +1672,194 @@ def tsdf_surface(state: dict, unobserved: str = "auto", close_border: bool = Tru
     :func:`ray_cast` take it as it is."""
     field, _ = tsdf_field(state, unobserved, close_border)
     return iso_surface(field, 0.0, state["lo"], state["step"])
+
+
+BAKE_MAX_CHANNELS = 16      # the channel and power limits of mofa_bake_integrate
+BAKE_MAX_POWER = 8
+BAKE_MAX_FILL = 10000
+_BAKE_COUNTS = ("colored", "occluded", "grazing", "unseen")       # MOFA_BAKE_* of the header
+_BAKE_BLEND = {"mean": 0, "best": 1}                               # MOFA_BAKE_MEAN / _BEST
+_BAKE_STATE = (("csum", torch.float64, True), ("wsum", torch.float64, False), ("wbest", torch.float64, False), ("cbest", torch.float32, True),
+               ("seen", torch.int32, False), ("occluded", torch.int32, False), ("grazing", torch.int32, False))
+
+
+def bake_state(V: int, channels: int = 3, device="cuda") -> dict:
+    """An empty colour-baking state for a mesh of ``V`` vertices: what :func:`bake_integrate` updates frame by frame.  A dict of seven
+    zeroed GPU tensors — ``csum [V,C]`` (float64, the weighted colour sum), ``wsum [V]`` (float64, the weight sum), ``wbest [V]`` (float64,
+    the largest weight so far), ``cbest [V,C]`` (float32, the colour of the view with the largest weight so far), ``seen``, ``occluded``
+    and ``grazing [V]`` (int32: the views that entered, those in which the vertex failed the depth test, those the angle test rejected) —
+    plus ``V``, ``channels`` and ``frames``.  20 C + 28 bytes per vertex; refused for ``V`` outside 0 .. 2^31 - 1, ``channels`` outside
+    1 .. 16 or a device that is no GPU."""
+    who = "bake_state"
+    if isinstance(V, (bool, np.bool_)) or not isinstance(V, (int, np.integer)) or not 0 <= int(V) <= INT32_MAX:
+        raise lib.MofaError(f"{who}: V = {V!r} (want an integer 0 .. 2^31 - 1)")
+    if isinstance(channels, (bool, np.bool_)) or not isinstance(channels, (int, np.integer)) or not 1 <= int(channels) <= BAKE_MAX_CHANNELS:
+        raise lib.MofaError(f"{who}: channels = {channels!r} (want an integer 1 .. {BAKE_MAX_CHANNELS})")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise lib.MofaError(f"{who}: the HIP path needs a GPU (got device {dev}); there is no CPU fallback")
+    V, C_ = int(V), int(channels)
+    state = {name: torch.zeros((V, C_) if per_channel else (V,), dtype=dtype, device=dev) for name, dtype, per_channel in _BAKE_STATE}
+    state.update(V=V, channels=C_, frames=0)
+    return state
+
+
+def _bake_state(who, state):
+    """(V, C, device) of a baking state, its tensors checked."""
+    if not isinstance(state, dict) or any(k not in state for k in ("V", "channels") + tuple(n for n, _, _ in _BAKE_STATE)):
+        raise lib.MofaError(f"{who}: want the state dict of bake_state")
+    V, C_ = int(state["V"]), int(state["channels"])
+    if not (0 <= V <= INT32_MAX and 1 <= C_ <= BAKE_MAX_CHANNELS):
+        raise lib.MofaError(f"{who}: the state has V = {V}, channels = {C_} (want 0 .. 2^31 - 1 and 1 .. {BAKE_MAX_CHANNELS})")
+    dev = state["csum"].device if torch.is_tensor(state["csum"]) else None
+    for name, dtype, per_channel in _BAKE_STATE:
+        t = state[name]
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise lib.MofaError(f"the HIP path needs tensors on the GPU (got a CPU tensor as the state's {name}); there is no CPU fallback")
+        shape = (V, C_) if per_channel else (V,)
+        if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape or t.device != dev:
+            raise lib.MofaError(f"{who}: the state's {name} is {t.dtype} {tuple(t.shape)} on {t.device} (want contiguous {dtype} {list(shape)} on {dev})")
+    return V, C_, dev
+
+
+def _bake_params(who, depth_tol, cos_min, power):
+    """bake_integrate's parameters, checked before anything touches the GPU."""
+    try:
+        depth_tol, cos_min = float(depth_tol), float(cos_min)
+    except (TypeError, ValueError):
+        raise lib.MofaError(f"{who}: depth_tol = {depth_tol!r}, cos_min = {cos_min!r} (want numbers)") from None
+    if not (np.isfinite(depth_tol) and depth_tol >= 0):
+        raise lib.MofaError(f"{who}: depth_tol = {depth_tol} (want finite and >= 0)")
+    if not 0.0 <= cos_min < 1.0:                                              # (NaN fails both comparisons)
+        raise lib.MofaError(f"{who}: cos_min = {cos_min} (want 0 <= cos_min < 1)")
+    if isinstance(power, (bool, np.bool_)) or not isinstance(power, (int, np.integer)) or not 0 <= int(power) <= BAKE_MAX_POWER:
+        raise lib.MofaError(f"{who}: power = {power!r} (want an integer 0 .. {BAKE_MAX_POWER})")
+    return depth_tol, cos_min, int(power)
+
+
+def bake_integrate(state: dict, verts: torch.Tensor, images: torch.Tensor, depth: torch.Tensor, K, c2w, normals: Optional[torch.Tensor] = None,
+                   *, depth_tol, cos_min: float = 0.0, power: int = 2) -> dict:
+    """Project posed colour frames onto the vertices of a mesh and add what they show to a state of :func:`bake_state`
+    (``mofa_bake_integrate``).  ``verts [V,3]`` float32; ``images`` ``[n,H,W,C]`` or ``[H,W,C]`` float32 with the state's ``C``; ``depth``
+    ``[n,H,W]`` or ``[H,W]`` float32 in the encoding of :func:`depth_frame` — the RAY PARAMETER of ``get_rays`` at the surface the view
+    sees (normally :func:`rasterize` of the mesh itself through :func:`depth_frame`), ``+inf`` background, NaN or <= 0 unknown; ``K`` /
+    ``c2w`` one camera or one per frame as in :func:`tsdf_integrate`; ``normals [V,3]`` (:func:`vertex_normals`) or ``None``.
+
+    Per vertex and view, in the order of the frames and in fp64 (include/mofanerf_hip.h has every operation): the vertex is taken into the
+    camera with :func:`tsdf_integrate`'s projection; its footprint is the 2 x 2 pixels around ``(u, v)`` and must lie inside the frame.  A
+    background or unknown depth at any corner skips the view (the silhouette erodes by a pixel, which is wanted: a pixel on it mixes face
+    and background); ``t - D > depth_tol`` at any corner counts the view in ``occluded`` and skips it.  With normals, ``cosv`` is the cosine
+    between the normal and the direction to the camera: not ``> cos_min`` counts the view in ``grazing`` and skips it, otherwise the view
+    weighs ``cosv ** power`` (repeated products); without normals every view weighs 1.  The colour is the bilinear interpolation of the
+    four texels; a non-finite texel skips the view.  ``csum += w colour``, ``wsum += w``, and the colour of the view with the strictly
+    largest weight so far is kept in ``cbest``.  No atomics and a fixed order: the same frames give the same bytes, and frames streamed in
+    several calls give the bytes of one call with all of them.  Returns ``state`` (updated in place; ``state["frames"]`` counts).
+
+    ``depth_tol`` (scene units) is required: none has been measured for a trained face; it must exceed the depth's own error (the
+    rasteriser snaps vertices to 1/256 pixel) and stay below the thickness of what may not shine through.  ``cos_min`` and ``power`` are
+    untuned defaults.  Raises ``MofaError`` for CPU tensors, wrong dtypes or shapes, tensors on different devices, frames smaller than
+    2 x 2 or with ``H W >= 2^31``, camera counts that match neither 1 nor ``n``, and parameters out of range."""
+    who = "bake_integrate"
+    V, C_, dev = _bake_state(who, state)
+    depth_tol, cos_min, power = _bake_params(who, depth_tol, cos_min, power)
+    for name, t, cols in (("verts", verts, 3), ("normals", normals, 3)):
+        if t is None:
+            continue
+        lib.ptr(t)
+        if tuple(t.shape) != (V, cols) or t.device != dev:
+            raise lib.MofaError(f"{who}: {name} {tuple(t.shape)} on {t.device} (want [{V},{cols}] on {dev}, the state's)")
+    lib.ptr(images), lib.ptr(depth)
+    if images.dim() not in (3, 4) or depth.dim() != images.dim() - 1 or tuple(images.shape[:-1]) != tuple(depth.shape) or images.shape[-1] != C_:
+        raise lib.MofaError(f"{who}: images {tuple(images.shape)}, depth {tuple(depth.shape)} (want [n,H,W,{C_}] and [n,H,W], or [H,W,{C_}] and [H,W])")
+    if images.device != dev or depth.device != dev:
+        raise lib.MofaError(f"{who}: the state is on {dev}, the images on {images.device}, the depth on {depth.device}")
+    frames = depth.detach().reshape((-1,) + tuple(depth.shape[-2:]))
+    n, H, W = (int(v) for v in frames.shape)
+    if n < 1 or H < 2 or W < 2 or H * W > INT32_MAX:
+        raise lib.MofaError(f"{who}: {n} frames of H = {H}, W = {W} are refused (n >= 1, H, W >= 2, H W < 2^31)")
+    cams = _tsdf_cameras(who, K, c2w, n)
+    if V:
+        with torch.cuda.device(dev):
+            table = torch.from_numpy(cams).to(dev)
+            lib.check(lib.load().mofa_bake_integrate(lib.ptr(verts.detach()), lib.ptr(None if normals is None else normals.detach()), V,
+                                                     lib.ptr(images.detach()), lib.ptr(frames), n, H, W, C_, lib.ptr(table), int(cams.shape[0]),
+                                                     depth_tol, cos_min, power, state["csum"].data_ptr(), state["wsum"].data_ptr(),
+                                                     state["wbest"].data_ptr(), state["cbest"].data_ptr(), state["seen"].data_ptr(),
+                                                     state["occluded"].data_ptr(), state["grazing"].data_ptr(), lib.stream()), "mofa_bake_integrate")
+    state["frames"] = int(state.get("frames", 0)) + n
+    return state
+
+
+def bake_colors(state: dict, blend: str = "mean", fill: float = 0.0) -> dict:
+    """The vertex colours of a baking state (``mofa_bake_resolve``).  ``blend="mean"``: the weighted mean ``csum / wsum`` of the views that
+    entered, where ``wsum > 0``; ``"best"``: the colour of the single view with the largest weight (the earliest among equals), where
+    ``seen > 0`` — sharper, with seams where the best view changes.  Everywhere else the colour is ``fill`` and the vertex is not valid.
+    Returns ``colors [V,C]`` float32, ``valid [V]`` bool, ``seen [V]`` int32 (the state's) and ``counts``: ``colored``, then the uncoloured
+    vertices by reason — ``occluded`` (some view saw something in front of them), ``grazing`` (only the angle test rejected them) and
+    ``unseen`` (no view held them in a footprint with a known surface) — plus ``vertices`` and ``frames``; the four classes partition the
+    vertices, and reading them is the call's one host read.  :func:`fill_colors` closes the holes."""
+    who = "bake_colors"
+    V, C_, dev = _bake_state(who, state)
+    if blend not in _BAKE_BLEND:
+        raise lib.MofaError(f"{who}: blend = {blend!r} (want 'mean' or 'best')")
+    try:
+        fill = float(fill)
+    except (TypeError, ValueError):
+        raise lib.MofaError(f"{who}: fill = {fill!r} (want a number)") from None
+    colors = torch.empty((V, C_), dtype=torch.float32, device=dev)
+    valid = torch.empty(V, dtype=torch.uint8, device=dev)
+    counts = dict.fromkeys(_BAKE_COUNTS, 0)
+    if V:
+        with torch.cuda.device(dev):
+            ws = torch.empty(16 * ((V + 255) // 256), dtype=torch.uint8, device=dev)
+            n = torch.empty(len(_BAKE_COUNTS), dtype=torch.int64, device=dev)
+            lib.check(lib.load().mofa_bake_resolve(V, C_, state["csum"].data_ptr(), state["wsum"].data_ptr(), state["cbest"].data_ptr(),
+                                                   state["seen"].data_ptr(), state["occluded"].data_ptr(), state["grazing"].data_ptr(),
+                                                   _BAKE_BLEND[blend], fill, lib.ptr(colors), valid.data_ptr(), ws.data_ptr(), n.data_ptr(),
+                                                   lib.stream()), "mofa_bake_resolve")
+            counts = dict(zip(_BAKE_COUNTS, (int(v) for v in n.cpu())))
+    counts.update(vertices=V, frames=int(state.get("frames", 0)))
+    return {"colors": colors, "valid": valid.bool(), "counts": counts, "seen": state["seen"]}
+
+
+def fill_colors(colors: torch.Tensor, valid: torch.Tensor, faces: torch.Tensor, iterations: int):
+    """Fill the holes of baked vertex colours from their neighbours (``mofa_bake_fill``): ``iterations`` Jacobi steps over
+    :func:`vertex_adjacency`'s lists, double-buffered.  In a step every invalid vertex with at least one valid neighbour takes the mean of
+    its valid neighbours' colours OF THE STEP'S INPUT (an fp64 sum in the adjacency's ascending order, one division, rounded to float32
+    once) and turns valid; everything else is copied — the front advances one edge per step, and a colour that was baked never changes.
+    ``colors [V,C]`` float32, ``valid [V]`` bool, ``faces [F,3]`` int32.  Returns ``(colors, valid, remaining)``: new tensors and the
+    number of vertices still invalid (the call's host read) — not 0 when ``iterations`` is too small, or for a component with no valid
+    vertex at all.  A face index outside [0, V) raises ``MofaError`` before any step runs; so do CPU tensors."""
+    who = "fill_colors"
+    lib.ptr(colors)
+    if colors.dim() != 2 or not 1 <= colors.shape[1] <= BAKE_MAX_CHANNELS:
+        raise lib.MofaError(f"{who}: want colors [V,C] with 1 <= C <= {BAKE_MAX_CHANNELS}, got {tuple(colors.shape)}")
+    V, C_, dev = int(colors.shape[0]), int(colors.shape[1]), colors.device
+    if not torch.is_tensor(valid) or not valid.is_cuda:
+        raise lib.MofaError(f"{who}: the HIP path needs tensors on the GPU (got a CPU valid); there is no CPU fallback")
+    if valid.dtype != torch.bool or tuple(valid.shape) != (V,) or valid.device != dev:
+        raise lib.MofaError(f"{who}: valid is {valid.dtype} {tuple(valid.shape)} on {valid.device} (want bool [{V}] on {dev})")
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or not 0 <= int(iterations) <= BAKE_MAX_FILL:
+        raise lib.MofaError(f"{who}: iterations = {iterations!r} (want an integer 0 .. {BAKE_MAX_FILL})")
+    if V > INT32_MAX:
+        raise lib.MofaError(f"{who}: {V} vertices exceed the int32 indices (2^31 - 1)")
+    adj = vertex_adjacency(faces, V)                                          # validates the faces first
+    if faces.device != dev:
+        raise lib.MofaError(f"{who}: colors on {dev}, faces on {faces.device}")
+    cur, ok = colors.detach().clone(), valid.to(torch.uint8).contiguous()
+    if ok is valid:
+        ok = ok.clone()
+    if V and int(iterations):
+        E = int(adj["neighbours"].shape[0])
+        with torch.cuda.device(dev):
+            nxt, ok_nxt = torch.empty_like(cur), torch.empty_like(ok)
+            for _ in range(int(iterations)):
+                lib.check(lib.load().mofa_bake_fill(lib.ptr(cur), ok.data_ptr(), V, C_, adj["offsets"].data_ptr(), adj["neighbours"].data_ptr(), E,
+                                                    lib.ptr(nxt), ok_nxt.data_ptr(), lib.stream()), "mofa_bake_fill")
+                cur, nxt, ok, ok_nxt = nxt, cur, ok_nxt, ok
+    ok = ok.bool()
+    remaining = int((~ok).sum().cpu()) if V else 0
+    return cur, ok, remaining
 
 
 SMOOTH_MAX_ITERATIONS = 1000

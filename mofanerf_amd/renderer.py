@@ -1138,6 +1138,78 @@ class Renderer(torch.nn.Module):
         self.check_launches(block=True)
         return verts, faces, stats
 
+    def bake_mesh(self, render_poses, H, W, K, verts, faces, *, depth_tol, shapeCodes, uvCodes, expCodes=None, expType=20, blend="mean",
+                  cos_min=0.0, power=2, fill_iterations=0, chunk=1024 * 32, normals=None, **render_kwargs):
+        """Vertex colours for a mesh with ANY triangulation — an extraction, or a template that was warped, simplified or smoothed off the
+        level set — from the renderer's own frames: per pose of ``render_poses`` one :meth:`render_fitting` colour frame (``ndc=False``,
+        compositing along every ray, texture code ``uvCodes``) is projected onto the vertices (``mesh.bake_integrate``) as soon as it is
+        rendered; no list of frames is kept.  What a vertex may take from a view is decided by the mesh itself: its visibility depth is
+        ``mesh.rasterize`` of ``verts`` / ``faces`` from that pose through ``mesh.depth_frame``, its normals are ``mesh.vertex_normals``
+        (or ``normals [V,3]``, e.g. ``extract_mesh``'s density normals).
+        Returns ``(colors [V,3] float32, valid [V] bool, stats)``; ``mesh.write_ply(colors=...)`` and :meth:`render_mesh` show them, and
+        colours of meshes in one vertex numbering stack into ``mesh.shape_model``.
+
+        ``depth_tol`` (scene units) is required: no value has been measured for a trained face.  ``blend``, ``cos_min`` and ``power`` are
+        ``mesh.bake_colors``' and ``mesh.bake_integrate``'s (untuned defaults); ``fill_iterations > 0`` closes the holes with
+        ``mesh.fill_colors``.  ``render_kwargs`` go to :meth:`render_fitting` (``near``, ``far``, ``occupancy`` and the
+        ``render_kwargs_test`` dictionary); ``ndc=True`` is refused as in :meth:`fuse_geometry`: the mesh lives in scene space.
+
+        ``stats``: ``mesh.bake_colors``' counts (``colored``, ``occluded``, ``grazing``, ``unseen``, ``vertices``, ``frames``) as they
+        stood BEFORE any filling, ``remaining`` (the vertices still invalid at the end), ``hit_share`` (per frame, the share of pixels the
+        mesh covers) and ``times`` (seconds spent rendering, rasterising, integrating and resolving, each phase waited for).
+        ``self.bake_stats`` keeps them, ``self.bake_state`` the state."""
+        from . import mesh
+        who = "bake_mesh"
+        if render_kwargs.pop("ndc", False):
+            raise lib.MofaError(f"{who}: ndc=True: the frames would be rendered in NDC space, the mesh lives in scene space (render with ndc=False)")
+        if blend not in ("mean", "best"):
+            raise lib.MofaError(f"{who}: blend = {blend!r} (want 'mean' or 'best')")
+        depth_tol, cos_min, power = mesh._bake_params(who, depth_tol, cos_min, power)
+        if isinstance(fill_iterations, bool) or not isinstance(fill_iterations, (int, np.integer)) or not 0 <= int(fill_iterations) <= mesh.BAKE_MAX_FILL:
+            raise lib.MofaError(f"{who}: fill_iterations = {fill_iterations!r} (want an integer 0 .. {mesh.BAKE_MAX_FILL})")
+        V, F, dev = mesh._mesh_tensors(who, verts, faces)
+        poses = [p for p in render_poses]
+        if not poses:
+            raise lib.MofaError(f"{who}: no poses")
+        H, W = int(H), int(W)
+        times = {"render": 0.0, "rasterize": 0.0, "integrate": 0.0, "resolve": 0.0}
+        shares = []
+        with torch.no_grad():
+            if normals is None:
+                normals = mesh.vertex_normals(verts, faces).contiguous()
+            state = mesh.bake_state(V, 3, dev)
+            for pose in poses:
+                t0 = time.perf_counter()
+                rgb = self.render_fitting(H, W, K, chunk=chunk, c2w=pose, ndc=False, shapeCodes=shapeCodes, uvCodes=uvCodes, expType=expType,
+                                          expCodes=expCodes, **render_kwargs)[0]
+                torch.cuda.synchronize(dev)
+                t1 = time.perf_counter()
+                r = mesh.rasterize(verts, faces, H, W, K, pose)
+                frame = mesh.depth_frame(r["depth"], r["mask"], "empty")
+                torch.cuda.synchronize(dev)
+                t2 = time.perf_counter()
+                mesh.bake_integrate(state, verts, rgb.reshape(H, W, 3).contiguous(), frame, K, pose, normals, depth_tol=depth_tol, cos_min=cos_min,
+                                    power=power)
+                shares.append(r["mask"].float().mean())
+                torch.cuda.synchronize(dev)
+                t3 = time.perf_counter()
+                times["render"] += t1 - t0
+                times["rasterize"] += t2 - t1
+                times["integrate"] += t3 - t2
+            t0 = time.perf_counter()
+            baked = mesh.bake_colors(state, blend)
+            colors, valid, stats = baked["colors"], baked["valid"], dict(baked["counts"])
+            remaining = stats["vertices"] - stats["colored"]
+            if fill_iterations:
+                colors, valid, remaining = mesh.fill_colors(colors, valid, faces, int(fill_iterations))
+            torch.cuda.synchronize(dev)
+            times["resolve"] = time.perf_counter() - t0
+        stats.update(remaining=int(remaining), hit_share=[float(s) for s in torch.stack(shares).cpu()], times=times, blend=blend,
+                     depth_tol=depth_tol, cos_min=cos_min, power=power)
+        self.bake_state, self.bake_stats = state, stats
+        self.check_launches(block=True)
+        return colors, valid, stats
+
     def render_path_mesh(self, render_poses, hwf, K, verts, faces, colors=None, savedir=None, znear=1e-3, ambient=0.3, near=None, far=None,
                          name=None):
         """One :meth:`render_mesh` frame per pose: a turntable of an exported mesh at the cost of a z-buffer.  With ``savedir`` two 8-bit
