@@ -652,6 +652,60 @@ int mofa_bake_resolve(int64_t V, int32_t C, const double* csum, const double* ws
 int mofa_bake_fill(const float* colors_in, const uint8_t* valid_in, int64_t V, int32_t C, const int64_t* offsets, const int32_t* nbr, int64_t E,
                    float* colors_out, uint8_t* valid_out, void* stream);
 
+/* UV texture baking: the map between the texels of a texture image and the surface of a mesh with an OBJ-style per-corner UV layout (uvs
+ * [T,2] float, uv_faces [F,3] int32: uv_faces[f][k] is the UV of corner k of faces[f]; T != V and seams are normal), and the image-side
+ * operations around mofa_bake_integrate, which takes the texels' surface points as it takes vertices (mesh.py drives the passes:
+ * mesh.uv_locate / texel_map / texel_surface / texture_image / dilate_texture / sample_texture).  A texture is [Ht,Wt,C] float, row 0 at
+ * the top, 1 <= C <= 16, Ht Wt < 2^31: texel (i, j) has its centre at u = (j + 0.5) / Wt, v = 1 - (i + 0.5) / Ht, and a UV maps to the
+ * continuous texel coordinates x = u Wt - 0.5, y = (1 - v) Ht - 0.5; no wrap-around; UVs outside [0, 1] are legal and see no texel.  One
+ * thread per element; all arithmetic is fp64 on the fp32 inputs widened, every operation rounded separately (no FMA); no float or double
+ * atomics: the same input gives the same bytes every time; the only atomics are the integer counters (int64, DEVICE, zeroed by the caller,
+ * one atomic per wavefront).  Every kernel checks the indices it dereferences: a bad one is skipped and counted.  1 <= N, T, V, F <= 2^31 - 1.
+ *   mofa_uv_locate   for queries [N,2] (double, DEVICE) the UV triangle that holds each: face [N] (int32, -1: none) and bary [N,3] (double,
+ *                    NaN where none).  The faces are listed per cell of a 2-D grid over (u, v) by mofa_wind_bin_count / _emit on the UVs as
+ *                    a zero-padded [T,3] copy with axis = 2 (every cell a face's closed UV box touches; the faces they drop as flat have no
+ *                    UV area), sorted stably by cell into cell_start [cells + 1] / pair_face [P] exactly as for mofa_wind_query, with the
+ *                    same origin / cell / n and the same permutation `order` (NULL = the identity).  A query walks the list of the cell
+ *                    of (idx(q.u), idx(q.v)).  Against face f with UV corners A, B, C:
+ *                      D = (B.u - A.u) (C.v - A.v) - (B.v - A.v) (C.u - A.u);  D == 0 or not finite: the face is skipped
+ *                      edge k is the one opposite corner k (B -> C, C -> A, A -> B); of its endpoints P is the lexicographically smaller
+ *                      (u, then v) and Q the other:  E = (Q.u - P.u) (q.v - P.v) - (Q.v - P.v) (q.u - P.u), negated where the face runs
+ *                      the edge from Q to P, and negated again when D < 0 (a mirrored chart): e_k.  Two faces that share an edge - by
+ *                      index or, across a seam, by equal coordinates - compute the same bits up to an exact sign.
+ *                      inside: e_0 >= 0, e_1 >= 0, e_2 >= 0 (zeros count, so a point on a shared edge cannot fall between two faces) and
+ *                      S = (e_0 + e_1) + e_2 > 0;  bary_k = e_k / S;  among the containing faces the lowest index wins.
+ *                    counts[MOFA_UV_DEGENERATE] += the faces of the layout whose D is 0 or not finite, [MOFA_UV_NON_FINITE] += the queries
+ *                    with a non-finite coordinate (face -1), [MOFA_UV_MULTI] += the queries STRICTLY inside (all e_k > 0) two or more
+ *                    faces (overlapping charts), [MOFA_UV_TESTS] += the listed faces walked (depends on the grid; no result does: a face
+ *                    can hold q only where its box does, and idx is monotone).  P = 0: nothing is listed, pair_face may be NULL.
+ *   mofa_uv_surface  per element (face [N] int32, bary [N,3] double) a surface point and a unit normal (float [N,3] each): with X_k =
+ *                    verts[faces[f][k]],  point[a] = (float)((b0 X0[a] + b1 X1[a]) + b2 X2[a]);  with normals [V,3] (float, DEVICE) m =
+ *                    the same interpolation of the vertex normals, with NULL m = (X1 - X0) x (X2 - X0) (p = X1 - X0, r = X2 - X0: p.y r.z
+ *                    - p.z r.y, p.z r.x - p.x r.z, p.x r.y - p.y r.x; it follows the faces' winding);  len = sqrt((m.x m.x + m.y m.y) +
+ *                    m.z m.z);  normal = (float)(m / len), (0, 0, 0) unless len > 0 and finite.  A face outside [0, F) or a vertex index
+ *                    outside [0, V): point NaN, normal 0, counts[0] += 1.
+ *   mofa_uv_dilate   one gutter-filling step on the image grid, double-buffered (input and output must differ): an invalid texel with k >=
+ *                    1 valid texels among its 8 neighbours inside the image takes (float)(s / k) per channel, s = 0.0 then s = s +
+ *                    (double)texture_in[neighbour] over the valid ones in row-major order of the 3 x 3 window, and valid_out = 1; every
+ *                    other texel is copied (a baked texel never changes).  valid: uint8 [Ht,Wt].
+ *   mofa_uv_sample   the texture lookup of a rasterised view: per pixel face [N] (int32) and bary [N,3] (float), as mofa_raster_resolve
+ *                    writes them:  u = (b0 u0 + b1 u1) + b2 u2 over the corners' UVs, v likewise (doubles, never rounded to float);  x, y
+ *                    as above;  j0 = floor(x), fx = x - j0, i0 = floor(y), fy = y - i0;  the indices j0, j0 + 1, i0, i0 + 1 clamped to
+ *                    the image;  per channel a = c00 + fx (c10 - c00), b = c01 + fx (c11 - c01), out = (float)(a + fy (b - a)), c10 the
+ *                    texel (i0, j0 + 1) (mofa_bake_integrate's order).  face outside [0, F) (-1: nothing was hit), a UV index outside [0,
+ *                    T) or a non-finite u or v: `background`, counts[0] += 1.
+ * A null pointer, a count or an image size out of range, C outside 1 .. 16 or a grid out of range returns MOFA_EINVAL with a message. */
+enum { MOFA_UV_DEGENERATE = 0, MOFA_UV_NON_FINITE = 1, MOFA_UV_TESTS = 2, MOFA_UV_MULTI = 3, MOFA_UV_COUNTS = 4 };
+int mofa_uv_locate(const double* queries, int64_t N, const int64_t* order, const float* uvs, int64_t T, const int32_t* uv_faces, int64_t F,
+                   const double origin[2], const double cell[2], const int32_t n[2], const int32_t* cell_start, const int32_t* pair_face, int64_t P,
+                   int32_t* face, double* bary, int64_t* counts, void* stream);
+int mofa_uv_surface(const int32_t* face, const double* bary, int64_t N, const float* verts, int64_t V, const int32_t* faces, int64_t F,
+                    const float* normals, float* points, float* normals_out, int64_t* counts, void* stream);
+int mofa_uv_dilate(const float* texture_in, const uint8_t* valid_in, int32_t Ht, int32_t Wt, int32_t C, float* texture_out, uint8_t* valid_out,
+                   void* stream);
+int mofa_uv_sample(const int32_t* face, const float* bary, int64_t N, const float* uvs, int64_t T, const int32_t* uv_faces, int64_t F,
+                   const float* texture, int32_t Ht, int32_t Wt, int32_t C, float background, float* out, int64_t* counts, void* stream);
+
 /* Mesh smoothing: Taubin lambda | mu filtering of the vertices of a triangle mesh (verts [V,3] float, faces [F,3] int32) over a fixed-order
  * vertex adjacency (mesh.py drives the passes: mesh.vertex_adjacency, mesh.smooth; 1 <= V, F, E <= 2^31 - 1).  No float or double atomics and
  * a fixed summation order: the same input gives the same bytes every time; the only atomics are the integer counters

@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmofanerf_hip.so")
 SOURCES = ["mofa_mlp.hip", "mofa_rays.hip", "mofa_bwd.hip", "mofa_net.hip", "mofa_mesh.hip", "mofa_refine.hip", "mofa_occ.hip", "mofa_raster.hip", "mofa_cc.hip",
            "mofa_simp.hip", "mofa_dist.hip", "mofa_wind.hip", "mofa_smooth.hip", "mofa_raycast.hip", "mofa_fuse.hip", "mofa_icp.hip",
-           "mofa_warp.hip", "mofa_shape.hip", "mofa_bake.hip"]
+           "mofa_warp.hip", "mofa_shape.hip", "mofa_bake.hip", "mofa_uv.hip"]
 # -fvisibility=hidden: the library exports exactly the C ABI of include/mofanerf_hip.h (declared under a visibility pragma there);
 # the mofa_internal_* hand-offs between the translation units stay out of the dynamic symbol table
 # -fhip-fp32-correctly-rounded-divide-sqrt (the compiler's default, pinned here): k_point_normals' sqrtf and every fp32 division are the

@@ -114,6 +114,10 @@ SIGNATURES = {
                                       _fp, _fp, _fp, _fp]),
     "mofa_bake_resolve": (C.c_int, [_i64, _i32, _fp, _fp, _fp, _fp, _fp, _fp, _i32, C.c_float, _fp, _fp, _fp, _fp, _fp]),
     "mofa_bake_fill": (C.c_int, [_fp, _fp, _i64, _i32, _fp, _fp, _i64, _fp, _fp, _fp]),
+    "mofa_uv_locate": (C.c_int, [_fp, _i64, _fp, _fp, _i64, _fp, _i64, _d3, _d3, C.POINTER(_i32), _fp, _fp, _i64, _fp, _fp, _fp, _fp]),
+    "mofa_uv_surface": (C.c_int, [_fp, _fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _fp]),
+    "mofa_uv_dilate": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _fp, _fp, _fp]),
+    "mofa_uv_sample": (C.c_int, [_fp, _fp, _i64, _fp, _i64, _fp, _i64, _fp, _i32, _i32, _i32, C.c_float, _fp, _fp, _fp]),
     "mofa_smooth_corner_cots": (C.c_int, [_fp, _fp, _i64, _i64, _fp, _fp, _fp]),
     "mofa_smooth_edge_weights": (C.c_int, [_fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp]),
     "mofa_smooth_step": (C.c_int, [_fp, _i64, _fp, _fp, _i64, _fp, _fp, C.c_double, _fp, _fp, _fp]),

@@ -17,6 +17,9 @@ volume and march its zero level: a mesh with no density level to choose (``mofa_
 ``shape_project`` evaluate and invert it, ``shape_fit`` fits it to a mesh with a triangulation of its own (``mofa_shape_*``).
 ``bake_state`` / ``bake_integrate`` / ``bake_colors`` project posed colour frames onto a mesh's vertices, occlusion-aware through a depth
 frame per view, and ``fill_colors`` closes the holes over the vertex adjacency (``mofa_bake_*``).
+``texel_map`` / ``texel_surface`` / ``texture_state`` / ``texture_image`` do the same onto the texels of a texture image through a UV
+layout (``uv_locate``, ``dilate_texture``, ``sample_texture``: ``mofa_uv_*``); ``face_atlas`` gives a mesh without UVs a per-triangle
+layout, and ``write_obj`` / ``read_obj`` carry mesh, layout and texture as OBJ + MTL + PNG.
 
 ``Renderer.query_density`` and ``Renderer.extract_mesh`` are the user-facing entry points; this module holds the pieces they share.
 The mesh is watertight and consistently oriented (normals toward lower density); vertices and faces come out in a fixed order with
@@ -1860,6 +1863,537 @@ def fill_colors(colors: torch.Tensor, valid: torch.Tensor, faces: torch.Tensor, 
     ok = ok.bool()
     remaining = int((~ok).sum().cpu()) if V else 0
     return cur, ok, remaining
+
+
+# UV texture baking (mofa_uv_*).  A UV layout is OBJ-style and per corner: uvs [T,2] float32, uv_faces [F,3] int32,
+# uv_faces[f, k] the UV of corner k of faces[f].  A texture is [Ht,Wt,C] float32, row 0 at the top: texel (i, j) has its centre at
+# u = (j + 0.5) / Wt, v = 1 - (i + 0.5) / Ht.  uv_locate's grid of face lists is mofa_wind_bin_*'s over (u, v); its resolution changes
+# no bit of the result.
+UV_GRID_CAP = WIND_GRID_CAP
+UV_GRID_AUTO_CAP = 256
+_UV_COUNTS = ("degenerate", "non_finite_queries", "face_tests", "multi")       # MOFA_UV_* of the header
+
+
+def default_uv_grid(F: int):
+    """The resolution uv_locate picks for ``F`` UV faces: ``ceil(sqrt(F / 4))`` cells per side, 1 .. UV_GRID_AUTO_CAP."""
+    g = int(min(max(math.ceil(math.sqrt(max(int(F), 0) / 4.0)), 1), UV_GRID_AUTO_CAP))
+    return (g, g)
+
+
+def _uv_layout(who, uvs, uv_faces):
+    """(T, F, device) of a UV layout on the GPU: contiguous float32 uvs [T,2], contiguous int32 uv_faces [F,3]."""
+    if not torch.is_tensor(uvs):
+        raise lib.MofaError(f"{who}: want uvs as a float32 tensor [T,2] on the GPU, got {type(uvs).__name__}")
+    lib.ptr(uvs)
+    if uvs.dim() != 2 or uvs.shape[1] != 2:
+        raise lib.MofaError(f"{who}: want uvs [T,2], got {tuple(uvs.shape)}")
+    if not torch.is_tensor(uv_faces) or not uv_faces.is_cuda:
+        raise lib.MofaError(f"{who}: the HIP path needs tensors on the GPU (got CPU uv_faces); there is no CPU fallback")
+    if uv_faces.dtype != torch.int32 or not uv_faces.is_contiguous() or uv_faces.dim() != 2 or uv_faces.shape[1] != 3:
+        raise lib.MofaError(f"{who}: want contiguous int32 uv_faces [F,3], got {uv_faces.dtype} {tuple(uv_faces.shape)}")
+    if uv_faces.device != uvs.device:
+        raise lib.MofaError(f"{who}: uvs on {uvs.device}, uv_faces on {uv_faces.device}")
+    T, F = int(uvs.shape[0]), int(uv_faces.shape[0])
+    if T > INT32_MAX or F > INT32_MAX:
+        raise lib.MofaError(f"{who}: {T} UVs / {F} faces exceed the int32 indices (2^31 - 1)")
+    return T, F, uvs.device
+
+
+def _uv_grid_arg(who, grid):
+    if grid is not None:
+        g = np.asarray(grid).reshape(-1)
+        if g.size not in (1, 2) or g.dtype.kind not in "iu" or (g < 1).any() or (g > UV_GRID_CAP).any():
+            raise lib.MofaError(f"{who}: grid = {grid!r} (want None, an integer or two, 1 .. {UV_GRID_CAP} per side)")
+        grid = tuple(int(v) for v in (np.repeat(g, 2) if g.size == 1 else g))
+    return grid
+
+
+def _texture_size(who, size):
+    s = np.asarray(size).reshape(-1)
+    if isinstance(size, (bool, np.bool_)) or s.size not in (1, 2) or s.dtype.kind not in "iu" or (s < 1).any():
+        raise lib.MofaError(f"{who}: size = {size!r} (want a positive integer or (Ht, Wt))")
+    Ht, Wt = (int(v) for v in (np.repeat(s, 2) if s.size == 1 else s))
+    if Ht * Wt > INT32_MAX:
+        raise lib.MofaError(f"{who}: a texture of {Ht} x {Wt} texels exceeds the int32 indices (Ht Wt < 2^31)")
+    return Ht, Wt
+
+
+def _uv_validate(who, uvs, uv_faces, T, F):
+    """The layout's indices (mofa_cc_validate) and coordinates, before any other launch; returns the zero-padded [T,3] copy of the UVs."""
+    L = lib.load()
+    dev = uvs.device
+    stream = lib.stream()
+    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    lib.check(L.mofa_cc_validate(uv_faces.data_ptr(), F, T, bad.data_ptr(), stream), "mofa_cc_validate")
+    n_bad = int(bad.cpu()[0])
+    if n_bad:
+        raise lib.MofaError(f"{who}: {n_bad} of the {3 * F} UV indices lie outside [0, {T})")
+    padded = torch.zeros((T, 3), dtype=torch.float32, device=dev)
+    padded[:, :2] = uvs.detach()
+    bad.zero_()
+    lib.check(L.mofa_dist_validate(lib.ptr(padded), T, bad.data_ptr(), stream), "mofa_dist_validate")
+    n_bad = int(bad.cpu()[0])
+    if n_bad:
+        raise lib.MofaError(f"{who}: {n_bad} of the {2 * T} UV coordinates are not finite")
+    return padded
+
+
+def _uv_lists(who, uvs, uv_faces, T, F, grid):
+    """Validate a UV layout and bin its faces over (u, v) with mofa_wind_bin_count / _emit (the UVs as a zero-padded [T,3] copy, axis 2):
+    every cell a face's closed UV box touches lists it, which is all a containment test needs.  What every batch of queries shares."""
+    L = lib.load()
+    dev = uvs.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    stream = lib.stream()
+    padded = _uv_validate(who, uvs, uv_faces, T, F)
+    box = torch.stack([padded.amin(0), padded.amax(0)]).cpu().numpy()
+    if grid is None:
+        grid = default_uv_grid(F)
+    origin, cell = wind_grid(box[0], box[1], grid, 2)
+    o2, c2, n2 = (C.c_double * 2)(*origin), (C.c_double * 2)(*cell), (C.c_int32 * 2)(*grid)
+    n_cells = grid[0] * grid[1]
+    scratch = torch.zeros(len(_WIND_COUNTS), **i64)
+    per_face = torch.empty(F, **i64)
+    lib.check(L.mofa_wind_bin_count(lib.ptr(padded), uv_faces.data_ptr(), F, T, 2, o2, c2, n2, per_face.data_ptr(), scratch.data_ptr(), stream),
+              "mofa_wind_bin_count")
+    ends = torch.cumsum(per_face, 0)
+    P = int(ends[-1].cpu())
+    if P > INT32_MAX:
+        raise lib.MofaError(f"{who}: the {F} UV faces enter {P} cells of the {grid} grid, more than 2^31 - 1: take a coarser grid")
+    start = torch.zeros(n_cells + 1, dtype=torch.int32, device=dev)
+    pair_face = torch.empty(P, dtype=torch.int32, device=dev)
+    if P:
+        offsets = (ends - per_face).contiguous()
+        pair_cell = torch.empty(P, dtype=torch.int32, device=dev)
+        lib.check(L.mofa_wind_bin_emit(lib.ptr(padded), uv_faces.data_ptr(), F, T, 2, o2, c2, n2, offsets.data_ptr(), P, pair_cell.data_ptr(),
+                                       pair_face.data_ptr(), stream), "mofa_wind_bin_emit")
+        if n_cells > 1:
+            by_cell = torch.sort(pair_cell, stable=True).indices
+            pair_face = pair_face[by_cell].contiguous()
+        start[1:] = torch.cumsum(torch.bincount(pair_cell.long(), minlength=n_cells), 0).to(torch.int32)
+    return dict(grid=grid, origin=origin, cell=cell, o2=o2, c2=c2, n2=n2, start=start, pair_face=pair_face, P=P)
+
+
+def _uv_query(queries, N, uvs, uv_faces, T, F, b):
+    """(face [N] int32, bary [N,3] float64, counts) of one batch of queries against the lists ``b`` of :func:`_uv_lists`."""
+    dev = uvs.device
+    grid = b["grid"]
+    face = torch.empty(N, dtype=torch.int32, device=dev)
+    bary = torch.empty((N, 3), dtype=torch.float64, device=dev)
+    counts = torch.zeros(len(_UV_COUNTS), dtype=torch.int64, device=dev)
+    order = None
+    if grid[0] * grid[1] > 1:                    # queries of one cell next to each other: a wavefront's lanes walk the same list
+        t = torch.nan_to_num((queries - torch.from_numpy(b["origin"]).to(dev)) / torch.from_numpy(b["cell"]).to(dev), nan=0.0, posinf=0.0,
+                             neginf=0.0).floor_()
+        hi = torch.tensor([g - 1 for g in grid], dtype=torch.float64, device=dev)
+        c = torch.minimum(torch.clamp_(t, min=0.0), hi).long()
+        order = torch.argsort(c[:, 0] * grid[1] + c[:, 1])
+        del t, c
+    lib.check(lib.load().mofa_uv_locate(queries.data_ptr(), N, None if order is None else order.data_ptr(), lib.ptr(uvs.detach()), T,
+                                        uv_faces.data_ptr(), F, b["o2"], b["c2"], b["n2"], b["start"].data_ptr(),
+                                        b["pair_face"].data_ptr() if b["P"] else None, b["P"], face.data_ptr(), bary.data_ptr(), counts.data_ptr(),
+                                        lib.stream()), "mofa_uv_locate")
+    return face, bary, dict(zip(_UV_COUNTS, (int(v) for v in counts.cpu())))
+
+
+def _uv_locate(who, queries, N, uvs, uv_faces, T, F, grid):
+    dev = uvs.device
+    if N == 0 or T == 0 or F == 0:
+        counts = dict.fromkeys(_UV_COUNTS, 0)
+        if N:
+            counts["non_finite_queries"] = int((~torch.isfinite(queries).all(1)).sum())
+        return (torch.full((N,), -1, dtype=torch.int32, device=dev), torch.full((N, 3), float("nan"), dtype=torch.float64, device=dev), counts,
+                grid if grid is not None else (1, 1))
+    with torch.cuda.device(dev):
+        b = _uv_lists(who, uvs, uv_faces, T, F, grid)
+        face, bary, counts = _uv_query(queries, N, uvs, uv_faces, T, F, b)
+    return face, bary, counts, b["grid"]
+
+
+def uv_locate(queries: torch.Tensor, uvs: torch.Tensor, uv_faces: torch.Tensor, grid=None) -> dict:
+    """The UV triangle that holds each of ``queries [N,2] float64`` (u, v), on the GPU (``mofa_uv_locate``).  Returns a dict: ``face [N]
+    int32`` (-1: none), ``bary [N,3] float64`` (NaN where none; ``bary[:, k]`` weighs corner ``k``), ``counts`` (``degenerate``: the UV
+    faces with no area, which hold nothing; ``non_finite_queries``; ``face_tests``; ``multi``: the queries strictly inside two or more
+    faces, which marks overlapping charts) and ``grid``.
+
+    The arithmetic is fixed (include/mofanerf_hip.h): an edge function is evaluated on the edge's endpoints in COORDINATE order, so the two
+    faces of an edge — also across a seam, where the edge has other UV indices but equal coordinates — see the same bits up to an exact
+    sign; zeros count as inside and the lowest face wins, so a point on a shared edge never falls between two faces.  Mirrored charts
+    (``D < 0``) are located like any other.  ``grid`` — ``None`` (``default_uv_grid``), an int or a pair, 1 .. UV_GRID_CAP per side —
+    changes the time but no bit of the result; ``grid=1`` is brute force through the same kernel.  There is no wrap-around: a query outside
+    every chart gets -1.  ``N``, ``T`` or ``F`` of 0 return without a launch.
+
+    Raises ``MofaError`` for CPU tensors, wrong dtypes or shapes, tensors on different devices, a grid out of range, a UV index outside
+    ``[0, T)`` (``mofa_cc_validate``) and a non-finite UV coordinate, all before the query runs."""
+    who = "uv_locate"
+    T, F, dev = _uv_layout(who, uvs, uv_faces)
+    if not torch.is_tensor(queries) or not queries.is_cuda:
+        raise lib.MofaError(f"{who}: the HIP path needs tensors on the GPU (got CPU queries); there is no CPU fallback")
+    if queries.dtype != torch.float64 or not queries.is_contiguous() or queries.dim() != 2 or queries.shape[1] != 2:
+        raise lib.MofaError(f"{who}: want contiguous float64 queries [N,2], got {queries.dtype} {tuple(queries.shape)}")
+    if queries.device != dev:
+        raise lib.MofaError(f"{who}: uvs on {dev}, queries on {queries.device}")
+    N = int(queries.shape[0])
+    if N > INT32_MAX:
+        raise lib.MofaError(f"{who}: {N} queries exceed the int32 indices (2^31 - 1)")
+    grid = _uv_grid_arg(who, grid)
+    face, bary, counts, grid = _uv_locate(who, queries.detach(), N, uvs, uv_faces, T, F, grid)
+    return {"face": face, "bary": bary, "counts": counts, "grid": grid}
+
+
+def texel_centres(size, device="cuda") -> torch.Tensor:
+    """float64 [Ht Wt, 2]: the (u, v) of every texel centre, row-major: ``u = (j + 0.5) / Wt``, ``v = 1 - (i + 0.5) / Ht``."""
+    Ht, Wt = _texture_size("texel_centres", size)
+    f64 = dict(dtype=torch.float64, device=device)          # (a tensor divisor: dividing by a Python scalar multiplies by its reciprocal on the GPU)
+    u = (torch.arange(Wt, **f64) + 0.5) / torch.full((Wt,), float(Wt), **f64)
+    v = 1.0 - (torch.arange(Ht, **f64) + 0.5) / torch.full((Ht,), float(Ht), **f64)
+    return torch.stack([u[None, :].expand(Ht, Wt), v[:, None].expand(Ht, Wt)], -1).reshape(-1, 2).contiguous()
+
+
+def texel_map(uvs: torch.Tensor, uv_faces: torch.Tensor, size, grid=None) -> dict:
+    """The map from the texels of a ``size`` (an int or ``(Ht, Wt)``) texture to the surface: :func:`uv_locate` of every texel centre.
+    Returns a dict: ``face [Ht,Wt] int32`` (-1: the texel lies in no chart), ``bary [Ht,Wt,3] float64``, ``covered [Ht,Wt] bool``,
+    ``index [M] int64`` (the covered texels' flat indices, row-major), ``counts`` (``covered`` = M; ``multi``: texels strictly inside two
+    or more faces — overlapping charts, of which the lowest face wins; ``degenerate``: UV faces without area; ``faces_without_texels``:
+    faces that own no texel — degenerate, hidden under a lower-numbered chart, outside [0, 1]^2 or thinner than the texel grid;
+    ``face_tests``), ``size`` = ``(Ht, Wt)``, ``grid`` and ``n_faces``.  Refusals as :func:`uv_locate`; ``Ht Wt >= 2^31`` is refused."""
+    who = "texel_map"
+    T, F, dev = _uv_layout(who, uvs, uv_faces)
+    Ht, Wt = _texture_size(who, size)
+    grid = _uv_grid_arg(who, grid)
+    with torch.cuda.device(dev):
+        face, bary, counts, grid = _uv_locate(who, texel_centres((Ht, Wt), dev), Ht * Wt, uvs, uv_faces, T, F, grid)
+        covered = face >= 0
+        index = torch.nonzero(covered).reshape(-1)
+        owners = int(torch.unique(face[index]).numel())
+    out_counts = {"covered": int(index.numel()), "multi": counts["multi"], "degenerate": counts["degenerate"], "faces_without_texels": F - owners,
+                  "face_tests": counts["face_tests"]}
+    return {"face": face.reshape(Ht, Wt), "bary": bary.reshape(Ht, Wt, 3), "covered": covered.reshape(Ht, Wt), "index": index,
+            "counts": out_counts, "size": (Ht, Wt), "grid": grid, "n_faces": F}
+
+
+def _texel_map_arg(who, tmap):
+    """((Ht, Wt), M, device) of a texel map, its tensors checked."""
+    keys = ("face", "bary", "covered", "index", "size", "n_faces")
+    if not isinstance(tmap, dict) or any(k not in tmap for k in keys):
+        raise lib.MofaError(f"{who}: want the dict of texel_map")
+    Ht, Wt = _texture_size(who, tmap["size"])
+    face, bary, index = tmap["face"], tmap["bary"], tmap["index"]
+    for name, t, dtype, shape in (("face", face, torch.int32, (Ht, Wt)), ("bary", bary, torch.float64, (Ht, Wt, 3)),
+                                  ("index", index, torch.int64, None)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise lib.MofaError(f"{who}: the HIP path needs tensors on the GPU (got a CPU tensor as the map's {name}); there is no CPU fallback")
+        if t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape) or t.device != face.device:
+            raise lib.MofaError(f"{who}: the map's {name} is {t.dtype} {tuple(t.shape)} on {t.device} (want contiguous {dtype} on {face.device})")
+    if index.dim() != 1:
+        raise lib.MofaError(f"{who}: the map's index is {tuple(index.shape)} (want [M])")
+    return (Ht, Wt), int(index.numel()), face.device
+
+
+def texel_surface(tmap: dict, verts: torch.Tensor, faces: torch.Tensor, normals: Optional[torch.Tensor] = None):
+    """``(points [M,3], normals [M,3])`` float32: the surface point and the unit normal of every covered texel of :func:`texel_map`, in the
+    order of its ``index`` (``mofa_uv_surface``): the barycentric interpolation of the face's vertices in fp64, rounded to float32 once,
+    and the interpolation of ``normals [V,3]`` normalised — or, with ``normals=None``, the face's flat normal ``(X1 - X0) x (X2 - X0)``,
+    which follows the faces' winding (a mesh wound with its normals inward needs ``normals=``: :func:`bake_integrate` calls every view of
+    an inward normal grazing).  A normal without length is (0, 0, 0).  These are the ``verts`` and ``normals`` :func:`bake_integrate` takes.
+    ``faces`` must be the mesh the layout belongs to (``F`` equal to the layout's); a face index outside ``[0, V)`` raises ``MofaError``."""
+    who = "texel_surface"
+    (Ht, Wt), M, dev = _texel_map_arg(who, tmap)
+    V, F, mdev = _mesh_tensors(who, verts, faces)
+    if mdev != dev:
+        raise lib.MofaError(f"{who}: the map is on {dev}, the mesh on {mdev}")
+    if F != int(tmap["n_faces"]):
+        raise lib.MofaError(f"{who}: the mesh has {F} faces, the UV layout of the map {int(tmap['n_faces'])}")
+    if normals is not None:
+        lib.ptr(normals)
+        if tuple(normals.shape) != (V, 3) or normals.device != dev:
+            raise lib.MofaError(f"{who}: normals {tuple(normals.shape)} on {normals.device} (want [{V},3] on {dev})")
+    points = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    out_normals = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    if M == 0:
+        return points, out_normals
+    if V == 0 or F == 0:
+        raise lib.MofaError(f"{who}: {M} covered texels, but the mesh has {V} vertices and {F} faces")
+    with torch.cuda.device(dev):
+        L = lib.load()
+        bad = torch.zeros(1, dtype=torch.int64, device=dev)
+        lib.check(L.mofa_cc_validate(faces.data_ptr(), F, V, bad.data_ptr(), lib.stream()), "mofa_cc_validate")
+        n_bad = int(bad.cpu()[0])
+        if n_bad:
+            raise lib.MofaError(f"{who}: {n_bad} of the {3 * F} face indices lie outside [0, {V})")
+        index = tmap["index"]
+        face = tmap["face"].reshape(-1)[index].contiguous()
+        bary = tmap["bary"].reshape(-1, 3)[index].contiguous()
+        bad.zero_()
+        lib.check(L.mofa_uv_surface(face.data_ptr(), bary.data_ptr(), M, lib.ptr(verts.detach()), V, faces.data_ptr(), F,
+                                    lib.ptr(None if normals is None else normals.detach()), lib.ptr(points), lib.ptr(out_normals), bad.data_ptr(),
+                                    lib.stream()), "mofa_uv_surface")
+    return points, out_normals
+
+
+def texture_state(tmap: dict, channels: int = 3) -> dict:
+    """``bake_state(M, channels)`` for the ``M`` covered texels of a :func:`texel_map`: frames go in through :func:`bake_integrate` with
+    :func:`texel_surface`'s points and normals — the integration kernel, its streaming and its bit-for-bit properties are the vertices'."""
+    _, M, dev = _texel_map_arg("texture_state", tmap)
+    return bake_state(M, channels, dev)
+
+
+def dilate_texture(texture: torch.Tensor, valid: torch.Tensor, iterations: int):
+    """Fill the gutters around the charts of a texture (``mofa_uv_dilate``): ``iterations`` steps on the image grid, double-buffered.  In a
+    step every invalid texel with at least one valid texel among its 8 neighbours (inside the image: no wrap-around) takes the mean of their
+    colours OF THE STEP'S INPUT (an fp64 sum in row-major order of the 3 x 3 window, one division, rounded to float32 once) and turns
+    valid; everything else is copied — the front advances one texel per step and a baked texel never changes.  This is what a bilinear
+    lookup at a chart's border reads.  ``texture [Ht,Wt,C]`` float32, ``valid [Ht,Wt]`` bool.  Returns ``(texture, valid, remaining)``: new
+    tensors and the texels still invalid (the call's host read)."""
+    who = "dilate_texture"
+    lib.ptr(texture)
+    if texture.dim() != 3 or not 1 <= texture.shape[2] <= BAKE_MAX_CHANNELS or texture.shape[0] < 1 or texture.shape[1] < 1:
+        raise lib.MofaError(f"{who}: want texture [Ht,Wt,C] with 1 <= C <= {BAKE_MAX_CHANNELS}, got {tuple(texture.shape)}")
+    Ht, Wt, C_ = (int(v) for v in texture.shape)
+    dev = texture.device
+    if Ht * Wt > INT32_MAX:
+        raise lib.MofaError(f"{who}: a texture of {Ht} x {Wt} texels exceeds the int32 indices (Ht Wt < 2^31)")
+    if not torch.is_tensor(valid) or not valid.is_cuda:
+        raise lib.MofaError(f"{who}: the HIP path needs tensors on the GPU (got a CPU valid); there is no CPU fallback")
+    if valid.dtype != torch.bool or tuple(valid.shape) != (Ht, Wt) or valid.device != dev:
+        raise lib.MofaError(f"{who}: valid is {valid.dtype} {tuple(valid.shape)} on {valid.device} (want bool [{Ht},{Wt}] on {dev})")
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or not 0 <= int(iterations) <= BAKE_MAX_FILL:
+        raise lib.MofaError(f"{who}: iterations = {iterations!r} (want an integer 0 .. {BAKE_MAX_FILL})")
+    cur, ok = texture.detach().clone(), valid.to(torch.uint8).contiguous()
+    if int(iterations):
+        with torch.cuda.device(dev):
+            nxt, ok_nxt = torch.empty_like(cur), torch.empty_like(ok)
+            for _ in range(int(iterations)):
+                lib.check(lib.load().mofa_uv_dilate(lib.ptr(cur), ok.data_ptr(), Ht, Wt, C_, lib.ptr(nxt), ok_nxt.data_ptr(), lib.stream()),
+                          "mofa_uv_dilate")
+                cur, nxt, ok, ok_nxt = nxt, cur, ok_nxt, ok
+    ok = ok.bool()
+    return cur, ok, int((~ok).sum().cpu())
+
+
+def texture_image(state: dict, tmap: dict, blend: str = "mean", fill: float = 0.0, dilate: int = 0) -> dict:
+    """The texture image of a baking state over the covered texels of ``tmap``: :func:`bake_colors` (``blend``, ``fill``), scattered
+    through the map's ``index`` into ``[Ht,Wt,C]`` (``fill`` everywhere else), then ``dilate`` steps of :func:`dilate_texture`.  Returns a
+    dict: ``texture [Ht,Wt,C]`` float32, ``valid [Ht,Wt]`` bool, ``counts`` (:func:`bake_colors`' — ``colored``, ``occluded``, ``grazing``,
+    ``unseen``, ``vertices`` = the covered texels, ``frames`` — taken BEFORE dilation) and ``remaining`` (the texels invalid at the end:
+    everything farther than ``dilate`` texels from a coloured one)."""
+    who = "texture_image"
+    (Ht, Wt), M, dev = _texel_map_arg(who, tmap)
+    V, C_, sdev = _bake_state(who, state)
+    if V != M or sdev != dev:
+        raise lib.MofaError(f"{who}: the state holds {V} points on {sdev}, the map {M} covered texels on {dev}")
+    if isinstance(dilate, (bool, np.bool_)) or not isinstance(dilate, (int, np.integer)) or not 0 <= int(dilate) <= BAKE_MAX_FILL:
+        raise lib.MofaError(f"{who}: dilate = {dilate!r} (want an integer 0 .. {BAKE_MAX_FILL})")
+    baked = bake_colors(state, blend, fill)
+    with torch.cuda.device(dev):
+        texture = torch.full((Ht * Wt, C_), float(fill), dtype=torch.float32, device=dev)
+        valid = torch.zeros(Ht * Wt, dtype=torch.bool, device=dev)
+        texture[tmap["index"]] = baked["colors"]
+        valid[tmap["index"]] = baked["valid"]
+        texture, valid = texture.reshape(Ht, Wt, C_), valid.reshape(Ht, Wt)
+        if int(dilate):
+            texture, valid, remaining = dilate_texture(texture, valid, int(dilate))
+        else:
+            remaining = int((~valid).sum().cpu())
+    return {"texture": texture, "valid": valid, "counts": baked["counts"], "remaining": remaining}
+
+
+def sample_texture(texture: torch.Tensor, face: torch.Tensor, bary: torch.Tensor, uvs: torch.Tensor, uv_faces: torch.Tensor,
+                   background: float = 0.0) -> torch.Tensor:
+    """The texture lookup of a rasterised view (``mofa_uv_sample``): ``face [H,W] int32`` and ``bary [H,W,3] float32`` exactly as
+    ``rasterize(bary=True)`` returns them, ``texture [Ht,Wt,C]`` float32.  Per pixel the UV is the barycentric interpolation of the
+    corners' UVs in fp64 (never rounded to float32), the lookup bilinear between the four texel centres around it with clamp-to-edge, in
+    :func:`bake_integrate`'s order, rounded once.  Returns ``[H,W,C]`` float32; a pixel that hit nothing (``face < 0``) is ``background``.
+    Raises ``MofaError`` for CPU tensors, wrong dtypes or shapes, different devices, a UV index outside ``[0, T)`` and a non-finite UV."""
+    who = "sample_texture"
+    T, F, dev = _uv_layout(who, uvs, uv_faces)
+    lib.ptr(texture), lib.ptr(bary)
+    if texture.dim() != 3 or not 1 <= texture.shape[2] <= BAKE_MAX_CHANNELS or texture.shape[0] < 1 or texture.shape[1] < 1:
+        raise lib.MofaError(f"{who}: want texture [Ht,Wt,C] with 1 <= C <= {BAKE_MAX_CHANNELS}, got {tuple(texture.shape)}")
+    Ht, Wt, C_ = (int(v) for v in texture.shape)
+    if Ht * Wt > INT32_MAX:
+        raise lib.MofaError(f"{who}: a texture of {Ht} x {Wt} texels exceeds the int32 indices (Ht Wt < 2^31)")
+    if not torch.is_tensor(face) or not face.is_cuda:
+        raise lib.MofaError(f"{who}: the HIP path needs tensors on the GPU (got a CPU face map); there is no CPU fallback")
+    if face.dtype != torch.int32 or not face.is_contiguous() or face.dim() != 2:
+        raise lib.MofaError(f"{who}: want a contiguous int32 face map [H,W], got {face.dtype} {tuple(face.shape)}")
+    H, W = (int(v) for v in face.shape)
+    if tuple(bary.shape) != (H, W, 3):
+        raise lib.MofaError(f"{who}: bary {tuple(bary.shape)} (want [{H},{W},3], the face map's)")
+    if any(t.device != dev for t in (texture, face, bary)):
+        raise lib.MofaError(f"{who}: uvs on {dev}, texture on {texture.device}, face on {face.device}, bary on {bary.device}")
+    if H * W > INT32_MAX:
+        raise lib.MofaError(f"{who}: {H} x {W} pixels exceed the int32 indices (H W < 2^31)")
+    try:
+        background = float(background)
+    except (TypeError, ValueError):
+        raise lib.MofaError(f"{who}: background = {background!r} (want a number)") from None
+    out = torch.full((H, W, C_), background, dtype=torch.float32, device=dev)
+    if H * W == 0 or T == 0 or F == 0:
+        return out
+    with torch.cuda.device(dev):
+        _uv_validate(who, uvs, uv_faces, T, F)
+        n = torch.zeros(1, dtype=torch.int64, device=dev)
+        lib.check(lib.load().mofa_uv_sample(face.data_ptr(), lib.ptr(bary.detach()), H * W, lib.ptr(uvs.detach()), T, uv_faces.data_ptr(), F,
+                                            lib.ptr(texture.detach()), Ht, Wt, C_, background, lib.ptr(out), n.data_ptr(), lib.stream()),
+                  "mofa_uv_sample")
+    return out
+
+
+def face_atlas(n_faces: int, size, padding: float = 1.0):
+    """A deterministic per-triangle UV atlas for a mesh that has no UVs (an extraction, a simplification): ``(uvs [3 F, 2] float32,
+    uv_faces [F,3] int32, info)`` as NumPy arrays, closed-form in fp64 on the host.  Faces ``2k`` and ``2k + 1`` share the cell ``k``
+    (row-major from the top left) of an ``n x n`` grid over the texture, ``n = ceil(sqrt(ceil(F / 2)))``; each is a right triangle with the
+    winding of its face (``D > 0``), its legs ``padding`` texels inside the cell's border and its hypotenuse ``padding`` texels from the
+    cell's diagonal, face ``2k`` toward the cell's top-left corner, ``2k + 1`` toward its bottom-right.  Every edge is a seam and charts
+    are ``2 padding`` texels apart, so nothing bleeds between faces (``texel_map(...)["counts"]["multi"] == 0``).  ``size`` (an int or
+    ``(Ht, Wt)``) is refused, with the size that would do, when a cell cannot hold the insets plus legs of one texel.  ``info``: ``n``,
+    ``cell`` (``(h, w)`` in texels), ``padding``, ``size`` and ``min_size``.  The area is spent evenly per face, not per surface area."""
+    who = "face_atlas"
+    if isinstance(n_faces, (bool, np.bool_)) or not isinstance(n_faces, (int, np.integer)) or not 0 <= int(n_faces) <= INT32_MAX // 3:
+        raise lib.MofaError(f"{who}: n_faces = {n_faces!r} (want an integer 0 .. (2^31 - 1) / 3)")
+    Ht, Wt = _texture_size(who, size)
+    try:
+        p = float(padding)
+    except (TypeError, ValueError):
+        raise lib.MofaError(f"{who}: padding = {padding!r} (want a number)") from None
+    if not (np.isfinite(p) and p >= 0):
+        raise lib.MofaError(f"{who}: padding = {padding!r} (want finite and >= 0)")
+    F = int(n_faces)
+    n = max(int(math.ceil(math.sqrt(math.ceil(F / 2)))), 1)
+    while n * n * 2 < F:                                                          # (sqrt rounded down on a perfect square)
+        n += 1
+    h, w = Ht / n, Wt / n
+    d = p * math.sqrt(1.0 / (w * w) + 1.0 / (h * h))                              # the hypotenuse's offset from the diagonal x / w + y / h = 1
+    leg_x, leg_y = w * (1.0 - d - p / h) - p, h * (1.0 - d - p / w) - p
+    min_size = n * int(math.ceil(1.0 + (2.0 + math.sqrt(2.0)) * p))
+    if not (leg_x >= 1.0 and leg_y >= 1.0):
+        raise lib.MofaError(f"{who}: {F} faces in {n} x {n} cells of {h:g} x {w:g} texels leave legs of {leg_y:g} x {leg_x:g} texels inside a "
+                            f"padding of {p:g}: want legs of at least one texel, which size = {min_size} gives")
+    k = np.arange(F, dtype=np.int64) // 2
+    x0, y0 = (k % n).astype(np.float64) * w, (k // n).astype(np.float64) * h    # the cell's top-left corner in texels (x right, y down)
+    upper = (np.arange(F) % 2 == 0)
+    # corner 0 at the right angle; then the corner along y and the corner along x, which in (u, v = 1 - y / Ht) is counter-clockwise
+    ax, ay = np.where(upper, x0 + p, x0 + w - p), np.where(upper, y0 + p, y0 + h - p)
+    bx, by = ax, np.where(upper, y0 + h * (1.0 - d - p / w), y0 + h * (d + p / w))
+    cx, cy = np.where(upper, x0 + w * (1.0 - d - p / h), x0 + w * (d + p / h)), ay
+    xy = np.stack([np.stack([ax, ay], -1), np.stack([bx, by], -1), np.stack([cx, cy], -1)], 1).reshape(-1, 2)
+    uvs = np.stack([xy[:, 0] / Wt, 1.0 - xy[:, 1] / Ht], -1).astype(np.float32)
+    uv_faces = np.arange(3 * F, dtype=np.int32).reshape(F, 3)
+    return uvs, uv_faces, {"n": n, "cell": (h, w), "padding": p, "size": (Ht, Wt), "min_size": min_size}
+
+
+def write_obj(path: str, verts, faces, uvs=None, uv_faces=None, normals=None, texture=None) -> None:
+    """Wavefront OBJ (text): ``v`` per vertex, ``vt`` per UV, ``vn`` per vertex normal, and ``f v``, ``f v/vt``, ``f v//vn`` or
+    ``f v/vt/vn`` per face, 1-based (normals are per vertex: ``vn`` index = ``v`` index).  With ``texture [Ht,Wt,3]`` (in [0, 1]) the
+    files ``<stem>.mtl`` and ``<stem>.png`` are written next to ``path`` — the texture through ``to8b`` and ``io.write_png``, row 0 at the
+    top, which is ``v = 1`` — and the OBJ names them (``mtllib``, ``usemtl``).  Plain host code: works without a GPU.  Floats are written
+    with 9 significant digits, so float32 values survive a round trip through :func:`read_obj`."""
+    import os
+    from . import io as mio
+    v = np.ascontiguousarray(_host(verts), dtype=np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(_host(faces), dtype=np.int64).reshape(-1, 3)
+    if (uvs is None) != (uv_faces is None):
+        raise ValueError("uvs and uv_faces go together")
+    stem = os.path.splitext(os.path.basename(path))[0]
+    folder = os.path.dirname(os.path.abspath(path))
+    lines = [f"# {len(v)} vertices, {len(f)} faces"]
+    if texture is not None:
+        if uvs is None:
+            raise ValueError("a texture needs uvs and uv_faces")
+        img = _host(texture)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"the texture must be [Ht,Wt,3], got {img.shape}")
+        mio.write_png(os.path.join(folder, stem + ".png"), to8b(img))
+        with open(os.path.join(folder, stem + ".mtl"), "w") as fh:
+            fh.write(f"newmtl {stem}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {stem}.png\n")
+        lines += [f"mtllib {stem}.mtl", f"usemtl {stem}"]
+    lines += ["v %.9g %.9g %.9g" % tuple(float(c) for c in row) for row in v]
+    if uvs is not None:
+        t = np.ascontiguousarray(_host(uvs), dtype=np.float32).reshape(-1, 2)
+        tf = np.ascontiguousarray(_host(uv_faces), dtype=np.int64).reshape(-1, 3)
+        if len(tf) != len(f):
+            raise ValueError(f"{len(tf)} UV faces for {len(f)} faces")
+        lines += ["vt %.9g %.9g" % tuple(float(c) for c in row) for row in t]
+    if normals is not None:
+        nrm = np.ascontiguousarray(_host(normals), dtype=np.float32).reshape(-1, 3)
+        if len(nrm) != len(v):
+            raise ValueError(f"{len(nrm)} normals for {len(v)} vertices")
+        lines += ["vn %.9g %.9g %.9g" % tuple(float(c) for c in row) for row in nrm]
+    for i, tri in enumerate(f + 1):
+        if uvs is not None and normals is not None:
+            lines.append("f " + " ".join(f"{a}/{b}/{a}" for a, b in zip(tri, tf[i] + 1)))
+        elif uvs is not None:
+            lines.append("f " + " ".join(f"{a}/{b}" for a, b in zip(tri, tf[i] + 1)))
+        elif normals is not None:
+            lines.append("f " + " ".join(f"{a}//{a}" for a in tri))
+        else:
+            lines.append("f " + " ".join(str(a) for a in tri))
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+def read_obj(path: str) -> dict:
+    """Read a Wavefront OBJ: a dict of NumPy arrays ``verts [V,3] float32``, ``faces [F,3] int32``, ``uvs [T,2] float32`` and ``uv_faces
+    [F,3] int32`` (both ``None`` when no face has a ``vt``), ``normals [V,3] float32`` (``None`` unless every corner names a ``vn``; the
+    ``vn`` of a vertex's LAST corner in file order is the vertex's) and ``mtllib`` (the file's, or ``None``).  Polygons are
+    fan-triangulated from their first corner; negative indices count back from the element read last; a face that mixes corners with and
+    without ``vt`` raises ``ValueError``; so does a file in which some faces have ``vt`` and others have none (``uv_faces`` has one row
+    per face or does not exist), and an index outside what has been read.  Plain host code: works without a GPU."""
+    v, vt, vn, faces, uv_faces, n_faces = [], [], [], [], [], []
+    mtllib = None
+    with open(path) as fh:
+        for ln, line in enumerate(fh, 1):
+            w = line.split("#", 1)[0].split()
+            if not w:
+                continue
+            if w[0] == "v":
+                v.append([float(c) for c in w[1:4]])
+            elif w[0] == "vt":
+                vt.append([float(c) for c in (w[1:3] + ["0"])[:2]])
+            elif w[0] == "vn":
+                vn.append([float(c) for c in w[1:4]])
+            elif w[0] == "mtllib":
+                mtllib = " ".join(w[1:])
+            elif w[0] == "f":
+                corners = []
+                for word in w[1:]:
+                    parts = (word.split("/") + ["", ""])[:3]
+                    idx = []
+                    for part, have in zip(parts, (len(v), len(vt), len(vn))):
+                        if part == "":
+                            idx.append(None)
+                            continue
+                        k = int(part)
+                        k = k - 1 if k > 0 else have + k
+                        if k < 0 or k >= have or int(part) == 0:
+                            raise ValueError(f"{path}:{ln}: index {part} outside the {have} elements read so far")
+                        idx.append(k)
+                    if idx[0] is None:
+                        raise ValueError(f"{path}:{ln}: a corner without a vertex index")
+                    corners.append(idx)
+                if len(corners) < 3:
+                    raise ValueError(f"{path}:{ln}: a face of {len(corners)} corners")
+                with_vt = [c[1] is not None for c in corners]
+                if any(with_vt) and not all(with_vt):
+                    raise ValueError(f"{path}:{ln}: a face that mixes corners with and without vt")
+                for k in range(1, len(corners) - 1):
+                    tri = (corners[0], corners[k], corners[k + 1])
+                    faces.append([c[0] for c in tri])
+                    uv_faces.append([c[1] for c in tri] if all(with_vt) else None)
+                    n_faces.append([c[2] for c in tri])
+    verts = np.asarray(v, np.float32).reshape(-1, 3)
+    out = {"verts": verts, "faces": np.asarray(faces, np.int32).reshape(-1, 3), "uvs": None, "uv_faces": None, "normals": None, "mtllib": mtllib}
+    if any(t is not None for t in uv_faces):
+        if any(t is None for t in uv_faces):
+            raise ValueError(f"{path}: faces with and faces without vt")
+        out["uvs"], out["uv_faces"] = np.asarray(vt, np.float32).reshape(-1, 2), np.asarray(uv_faces, np.int32).reshape(-1, 3)
+    if n_faces and all(k is not None for tri in n_faces for k in tri):
+        normals = np.zeros_like(verts)
+        table = np.asarray(vn, np.float32).reshape(-1, 3)
+        normals[out["faces"].reshape(-1)] = table[np.asarray(n_faces, np.int64).reshape(-1)]
+        out["normals"] = normals
+    return out
 
 
 SMOOTH_MAX_ITERATIONS = 1000
@@ -3730,4 +4264,5 @@ def read_ply(path: str):
 
 __all__: Sequence[str] = ("grid_spec", "grid_points", "iso_surface", "band_surface", "refine_vertices", "density_normals", "vertex_normals", "components", "select_components", "keep_components", "simplify", "closest_points", "sample_faces", "surface_distance", "dist_grid", "default_dist_grid", "winding_number", "signed_distance",
                            "inside_grid", "wind_grid", "default_wind_grid", "vertex_adjacency", "smooth", "rasterize", "depth_agreement", "to8b", "write_ply",
-                           "read_ply")
+                           "read_ply", "uv_locate", "texel_centres", "texel_map", "texel_surface", "texture_state", "texture_image", "dilate_texture",
+                           "sample_texture", "face_atlas", "default_uv_grid", "write_obj", "read_obj")

@@ -1018,16 +1018,35 @@ class Renderer(torch.nn.Module):
         out["rendered"], out["skipped"] = rendered, skipped
         return out
 
-    def render_mesh(self, H, W, K, c2w, verts, faces, colors=None, znear=1e-3, ambient=0.3):
+    def render_mesh(self, H, W, K, c2w, verts, faces, colors=None, znear=1e-3, ambient=0.3, texture=None, uvs=None, uv_faces=None):
         """A view of a triangle mesh — what :meth:`extract_mesh` returns — from the camera ``K`` / ``c2w`` of ``get_rays``, by the GPU
         rasteriser (``mesh.rasterize``; no network runs).  Returns ``(rgb [H,W,3], depth [H,W], mask [H,W] bool, extras)``; ``depth`` is
         the ray parameter of the pixel's ray, the depth :meth:`render_geometry` gives without NDC, and 0 where nothing is hit.  With
         ``colors [V,3]`` (``extract_mesh(colors=True)``) ``rgb`` is the perspective-correct interpolation of the vertex colours; without,
         a head-light shade of the flat face normal ``n`` (turned to the camera): ``ambient + (1 - ambient) max(0, -n . d / |d|)`` for
         the pixel's ray direction ``d``, black where nothing is hit.  ``extras``: ``face`` (int32, -1 where nothing is hit), ``counts``
-        (device int64 [4]: faces drawn, culled, degenerate, on the wavefront path) and, for the shade, ``normal``."""
+        (device int64 [4]: faces drawn, culled, degenerate, on the wavefront path) and, for the shade, ``normal``.
+
+        With ``texture [Ht,Wt,3]`` and the mesh's UV layout ``uvs [T,2]`` / ``uv_faces [F,3]`` (:meth:`bake_texture`, ``mesh.texel_map``)
+        ``rgb`` is ``mesh.sample_texture`` of the rasterised ``face`` / ``bary`` — a bilinear lookup per pixel, black where nothing is
+        hit — and ``extras`` holds ``bary`` too; like ``colors``, a texture is shown as it is: ``ambient`` belongs to the shade alone and
+        is not read.  ``colors`` together with ``texture`` is refused.  Without the three arguments nothing changes."""
         from . import mesh
         from .rays import get_rays
+        if texture is not None or uvs is not None or uv_faces is not None:
+            if colors is not None:
+                raise lib.MofaError("render_mesh: colors and texture are two ways to colour the mesh: give one")
+            if texture is None or uvs is None or uv_faces is None:
+                raise lib.MofaError("render_mesh: texture, uvs and uv_faces go together")
+            if not torch.is_tensor(texture) or texture.dim() != 3 or texture.shape[-1] != 3:
+                raise lib.MofaError(f"render_mesh: want texture [Ht,Wt,3], got {tuple(texture.shape) if torch.is_tensor(texture) else type(texture).__name__}")
+            _, F, _ = mesh._mesh_tensors("render_mesh", verts, faces)
+            if not torch.is_tensor(uv_faces) or uv_faces.dim() != 2 or uv_faces.shape[0] != F:
+                raise lib.MofaError(f"render_mesh: uv_faces {tuple(uv_faces.shape) if torch.is_tensor(uv_faces) else type(uv_faces).__name__} for "
+                                    f"{F} faces (want one row of UV indices per face)")
+            out = mesh.rasterize(verts, faces, H, W, K, c2w, znear=znear, bary=True)
+            rgb = mesh.sample_texture(texture, out["face"], out["bary"], uvs, uv_faces, background=0.0)
+            return rgb, out["depth"], out["mask"], {"face": out["face"], "counts": out["counts"], "bary": out["bary"]}
         if colors is not None:
             if colors.dim() != 2 or colors.shape[-1] != 3:
                 raise lib.MofaError(f"render_mesh: want colors [V,3], got {tuple(colors.shape)}")
@@ -1210,13 +1229,90 @@ class Renderer(torch.nn.Module):
         self.check_launches(block=True)
         return colors, valid, stats
 
+    def bake_texture(self, render_poses, H, W, K, verts, faces, uvs, uv_faces, *, size=512, depth_tol, shapeCodes, uvCodes, expCodes=None,
+                     expType=20, blend="mean", cos_min=0.0, power=2, dilate=8, normals=None, chunk=1024 * 32, **render_kwargs):
+        """A texture image for a mesh with a UV layout (``uvs [T,2]`` float32, ``uv_faces [F,3]`` int32, per corner as in an OBJ; a
+        template's own, or ``mesh.face_atlas`` for a mesh without one) from the renderer's own frames: :meth:`bake_mesh`'s loop with the
+        surface points of the texels in place of the vertices.  ``mesh.texel_map`` finds the face and barycentrics of every texel centre
+        of a ``size`` (an int or ``(Ht, Wt)``) image once, ``mesh.texel_surface`` makes their points and normals (the interpolation of
+        ``normals [V,3]``, default ``mesh.vertex_normals``); then per pose one :meth:`render_fitting` colour frame (``ndc=False``) is
+        projected onto them by ``mesh.bake_integrate`` against ``mesh.rasterize``'s depth of the mesh itself.  ``mesh.texture_image``
+        resolves (``blend``), scatters and fills the gutters (``dilate`` steps).
+        Returns ``(texture [Ht,Wt,3] float32, valid [Ht,Wt] bool, stats)``.  With ``size=512`` the texture is the tensor
+        ``render(uvMap=...)`` takes; ``mesh.write_obj(texture=...)`` writes OBJ + MTL + PNG, and :meth:`render_mesh` shows it.
+
+        ``depth_tol`` is required and ``blend``, ``cos_min``, ``power`` are untuned, as in :meth:`bake_mesh`; ``ndc=True`` is refused.
+        ``stats``: :meth:`bake_mesh`'s keys — the counts are over the covered texels (``vertices`` = their number), taken before dilation;
+        ``remaining`` the texels invalid at the end — plus the map's ``covered``, ``multi``, ``degenerate``, ``faces_without_texels``,
+        ``size``, and ``times["texel_map"]`` (the map and the surface points).  ``self.bake_stats`` / ``self.bake_state`` keep stats and
+        state, ``self.bake_map`` the texel map."""
+        from . import mesh
+        who = "bake_texture"
+        if render_kwargs.pop("ndc", False):
+            raise lib.MofaError(f"{who}: ndc=True: the frames would be rendered in NDC space, the mesh lives in scene space (render with ndc=False)")
+        if blend not in ("mean", "best"):
+            raise lib.MofaError(f"{who}: blend = {blend!r} (want 'mean' or 'best')")
+        depth_tol, cos_min, power = mesh._bake_params(who, depth_tol, cos_min, power)
+        if isinstance(dilate, bool) or not isinstance(dilate, (int, np.integer)) or not 0 <= int(dilate) <= mesh.BAKE_MAX_FILL:
+            raise lib.MofaError(f"{who}: dilate = {dilate!r} (want an integer 0 .. {mesh.BAKE_MAX_FILL})")
+        V, F, dev = mesh._mesh_tensors(who, verts, faces)
+        T, Fu, udev = mesh._uv_layout(who, uvs, uv_faces)
+        if Fu != F or udev != dev:
+            raise lib.MofaError(f"{who}: {Fu} UV faces on {udev} for {F} faces on {dev} (want one row of UV indices per face, on one device)")
+        size = mesh._texture_size(who, size)
+        poses = [p for p in render_poses]
+        if not poses:
+            raise lib.MofaError(f"{who}: no poses")
+        H, W = int(H), int(W)
+        times = {"texel_map": 0.0, "render": 0.0, "rasterize": 0.0, "integrate": 0.0, "resolve": 0.0}
+        shares = []
+        with torch.no_grad():
+            t0 = time.perf_counter()
+            if normals is None:
+                normals = mesh.vertex_normals(verts, faces).contiguous()
+            tmap = mesh.texel_map(uvs, uv_faces, size)
+            points, point_normals = mesh.texel_surface(tmap, verts, faces, normals)
+            state = mesh.texture_state(tmap, 3)
+            torch.cuda.synchronize(dev)
+            times["texel_map"] = time.perf_counter() - t0
+            for pose in poses:
+                t0 = time.perf_counter()
+                rgb = self.render_fitting(H, W, K, chunk=chunk, c2w=pose, ndc=False, shapeCodes=shapeCodes, uvCodes=uvCodes, expType=expType,
+                                          expCodes=expCodes, **render_kwargs)[0]
+                torch.cuda.synchronize(dev)
+                t1 = time.perf_counter()
+                r = mesh.rasterize(verts, faces, H, W, K, pose)
+                frame = mesh.depth_frame(r["depth"], r["mask"], "empty")
+                torch.cuda.synchronize(dev)
+                t2 = time.perf_counter()
+                mesh.bake_integrate(state, points, rgb.reshape(H, W, 3).contiguous(), frame, K, pose, point_normals, depth_tol=depth_tol,
+                                    cos_min=cos_min, power=power)
+                shares.append(r["mask"].float().mean())
+                torch.cuda.synchronize(dev)
+                t3 = time.perf_counter()
+                times["render"] += t1 - t0
+                times["rasterize"] += t2 - t1
+                times["integrate"] += t3 - t2
+            t0 = time.perf_counter()
+            image = mesh.texture_image(state, tmap, blend, 0.0, int(dilate))
+            torch.cuda.synchronize(dev)
+            times["resolve"] = time.perf_counter() - t0
+        stats = dict(image["counts"])
+        stats.update({k: tmap["counts"][k] for k in ("covered", "multi", "degenerate", "faces_without_texels")})
+        stats.update(remaining=int(image["remaining"]), hit_share=[float(s) for s in torch.stack(shares).cpu()], times=times, blend=blend,
+                     depth_tol=depth_tol, cos_min=cos_min, power=power, size=tmap["size"], dilate=int(dilate))
+        self.bake_state, self.bake_stats, self.bake_map = state, stats, tmap
+        self.check_launches(block=True)
+        return image["texture"], image["valid"], stats
+
     def render_path_mesh(self, render_poses, hwf, K, verts, faces, colors=None, savedir=None, znear=1e-3, ambient=0.3, near=None, far=None,
-                         name=None):
+                         name=None, texture=None, uvs=None, uv_faces=None):
         """One :meth:`render_mesh` frame per pose: a turntable of an exported mesh at the cost of a z-buffer.  With ``savedir`` two 8-bit
         PNGs per pose go through the ``PngSink``: ``<stem>_mesh.png`` (``rgb``) and ``<stem>_mesh_depth.png`` (``(depth - near) / (far -
         near)`` in grey, black where nothing is hit; ``near`` / ``far`` default to the least and greatest depth of the frame); ``stem`` as
         in :meth:`render_path_geometry`.  A pose whose two files exist is skipped.  Returns a dict of numpy arrays stacked over the
-        rendered poses — ``rgb``, ``depth``, ``mask``, ``face`` — with ``rendered`` and ``skipped``, the lists of pose numbers."""
+        rendered poses — ``rgb``, ``depth``, ``mask``, ``face`` — with ``rendered`` and ``skipped``, the lists of pose numbers.
+        ``texture`` / ``uvs`` / ``uv_faces`` are :meth:`render_mesh`'s: a textured turntable."""
         height, width, _ = hwf
         height, width = int(height), int(width)
         if (near is None) != (far is None) or (near is not None and not _scalar(far) > _scalar(near)):
@@ -1224,7 +1320,7 @@ class Renderer(torch.nn.Module):
 
         def frame(i, paths, sink):
             rgb, depth, mask, ex = self.render_mesh(height, width, K, render_poses[i][:3, :4], verts, faces, colors=colors, znear=znear,
-                                                    ambient=ambient)
+                                                    ambient=ambient, texture=texture, uvs=uvs, uv_faces=uv_faces)
             if paths is not None:
                 if near is None:
                     hit = depth[mask]
